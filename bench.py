@@ -7,6 +7,11 @@ JSON line; `value` is the whole-job aggregate sorted throughput in GB/s
 (BASELINE.json metric: 320 GB TeraSort wall-clock + shuffle-read GB/s —
 ms_per_step is the wall-clock of one complete sort job of the configured
 dataset; value = dataset_bytes / wall_clock aggregated over all ranks).
+
+A plain run does only what that line needs: set up, warm up, time the
+steps. `--dump-outputs DIR` additionally saves the last timed step's
+output as .npy files (seeded inputs: comparable run to run and build to
+build); `--full` adds the per-step phase breakdowns on stderr.
 """
 
 import argparse
@@ -27,6 +32,84 @@ def _fetch_rate(results, ts):
     rates = [(getattr(r, "records", 0) * rb / r.fetch_s) / 1e9
              for r in results if getattr(r, "fetch_s", 0) > 0]
     return round(sum(rates) / len(rates), 2) if rates else None
+
+
+# --dump-outputs budget: every file together stays far below 64 MB
+DUMP_SAMPLE_BYTES = 32 << 20     # float32 bytes of the sampled records
+DUMP_SEED = 0
+
+
+def _terasort_record_matrix(ts):
+    """The last framework-mode step's sorted output as one [n, W] uint8
+    matrix of whole records (torch on GPU, numpy on CPU), or None."""
+    outs = [o for o in (getattr(ts, "last_outputs", None) or [])
+            if o is not None and not (isinstance(o, tuple) and o[0] is None)]
+    if not outs:
+        return None
+    W = ts.RECORD_BYTES
+    if ts.device == "cuda":
+        import torch
+        # chunks share the reused sort buffers: only the last one is still
+        # intact after the step (one chunk == the whole output at 1 GPU)
+        o = outs[-1]
+        if isinstance(o, tuple):
+            # (keys, vals) are the even/odd views of one AoS pair buffer:
+            # re-span it as [n, 2] without copying
+            o = torch.as_strided(o[0], (o[0].numel(), 2), (2, 1))
+        return o.view(torch.uint8).reshape(-1, W)
+    import numpy as np
+    return np.concatenate(
+        [np.concatenate([np.ascontiguousarray(k).view(np.uint8).reshape(-1, 8),
+                         np.ascontiguousarray(v).view(np.uint8).reshape(-1, 8)],
+                        axis=1) for k, v in outs])
+
+
+def _dump_outputs(out_dir, ts, result):
+    """Write what the last timed step handed back as <name>.npy files:
+    the result record's counters, and for workloads that keep their output
+    arrays a seeded record sample plus whole-output column sums."""
+    import dataclasses
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    fields = [(f.name, getattr(result, f.name))
+              for f in dataclasses.fields(result)
+              if f.name != "seconds" and not f.name.endswith("_s")]
+    # one float64 per non-timing field, in declaration order
+    np.save(os.path.join(out_dir, "step_result.npy"),
+            np.array([float(v) for _, v in fields], dtype=np.float64))
+
+    ranks = getattr(ts, "ranks", None)        # PageRank's owned vertex slice
+    if ranks is not None:
+        if not isinstance(ranks, np.ndarray):
+            ranks = ranks.cpu().numpy()
+        np.save(os.path.join(out_dir, "ranks.npy"),
+                ranks.astype(np.float64)[:DUMP_SAMPLE_BYTES // 8])
+
+    mat = _terasort_record_matrix(ts) if hasattr(ts, "RECORD_BYTES") else None
+    if mat is None:
+        return
+    n, W = int(mat.shape[0]), int(mat.shape[1])
+    take = min(n, DUMP_SAMPLE_BYTES // (4 * W))
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.arange(n) if take == n else np.sort(rng.integers(0, n, take))
+    colsum = np.zeros(W, dtype=np.float64)
+    rows = 1 << 20                 # bounded temporaries on a 40 GB output
+    if isinstance(mat, np.ndarray):
+        sample = mat[idx]
+        for a in range(0, n, rows):
+            colsum += mat[a:a + rows].sum(axis=0, dtype=np.float64)
+    else:
+        import torch
+        sample = mat[torch.from_numpy(idx).to(mat.device)].cpu().numpy()
+        acc = torch.zeros(W, dtype=torch.float64, device=mat.device)
+        for a in range(0, n, rows):
+            acc += mat[a:a + rows].sum(dim=0, dtype=torch.float64)
+        colsum = acc.cpu().numpy()
+    np.save(os.path.join(out_dir, "sorted_records_sample.npy"),
+            sample.astype(np.float32))
+    np.save(os.path.join(out_dir, "sorted_records_sample_index.npy"),
+            idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "sorted_records_bytesum.npy"), colsum)
 
 
 def main():
@@ -53,6 +136,20 @@ def main():
                          "90B value — the flagship config; GPU only) or 16 "
                          "(u64 key + u64 payload; the CPU/rccl-mode shape)")
     ap.add_argument("--validate", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step "
+                         "returned as DIR/<name>.npy (float32/float64, "
+                         "< 64 MB): step_result (the result record's "
+                         "non-timing fields in declaration order), and for "
+                         "terasort a seeded sample of the sorted records "
+                         "with its row indices and per-byte-column sums of "
+                         "the whole output; inputs are seeded, so equal "
+                         "arguments give equal files")
+    ap.add_argument("--full", action="store_true",
+                    help="also report what the headline figure does not "
+                         "need: per-step phase breakdowns (write / fetch / "
+                         "sort) on stderr; a plain run only sets up, warms "
+                         "up, times the steps and prints the result line")
     ap.add_argument("--cpu", action="store_true",
                     help="force CPU path (plumbing debug)")
     args = ap.parse_args()
@@ -147,6 +244,8 @@ def main():
         if use_cuda:
             torch.cuda.synchronize()
 
+    if args.full:
+        os.environ.setdefault("BENCH_DEBUG", "1")
     debug = os.environ.get("BENCH_DEBUG")
     for _ in range(args.warmup):
         r = ts.run_step()
@@ -170,6 +269,15 @@ def main():
             t = t.cuda()
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.full and rank == 0:
+        for i, r in enumerate(results):
+            if hasattr(r, "write_s"):
+                print(f"[step {i}] total={r.seconds*1e3:.1f}ms "
+                      f"write={r.write_s*1e3:.1f} fetch={r.fetch_s*1e3:.1f} "
+                      f"sort={r.sort_s*1e3:.1f}", file=sys.stderr)
+    if args.dump_outputs and rank == 0 and results:
+        _dump_outputs(args.dump_outputs, ts, results[-1])
 
     ms_per_step = elapsed / args.steps * 1e3
     if args.workload == "terasort" and args.mode == "shuffleread":

@@ -62,6 +62,10 @@ class Driver:
         self._shuffles: Dict[int, _ShuffleMeta] = {}
         self._next_shuffle_id = 0
         self._lock = threading.Lock()
+        # membership snapshot + its fan-out are one unit: two connection
+        # threads announcing concurrently must not deliver an older
+        # snapshot after a newer one (executors keep the last they see)
+        self._announce_lock = threading.Lock()
         self._stopped = threading.Event()
         self._barrier_waiters: List[rpc.MsgConnection] = []
         self._barrier_gen = 0
@@ -105,6 +109,11 @@ class Driver:
         """Drop an executor (clean BYE or lost connection): prune
         membership, re-announce, and release any barrier the departure
         now satisfies (everyone still alive is already waiting)."""
+        with self._announce_lock:
+            self._prune_and_reannounce(conn, clean)
+
+    def _prune_and_reannounce(self, conn: rpc.MsgConnection,
+                              clean: bool) -> None:
         reannounce = None
         release = []
         with self._lock:
@@ -145,18 +154,20 @@ class Driver:
     def _dispatch(self, conn: rpc.MsgConnection, mtype: int, body: bytes) -> None:
         if mtype == rpc.MSG_HELLO:
             info = rpc.unpack_hello(body)
-            with self._lock:
-                self._members[info.executor_id] = info
-                self._conn_exec[conn] = info.executor_id
-                members = list(self._members.values())
-                conns = list(self._conns)
-            # fan out announce to every connected executor (reference :89-112)
-            payload = rpc.pack_announce(self.app_id, members)
-            for c in conns:
-                try:
-                    c.send(rpc.MSG_ANNOUNCE, payload)
-                except OSError:
-                    pass
+            with self._announce_lock:
+                with self._lock:
+                    self._members[info.executor_id] = info
+                    self._conn_exec[conn] = info.executor_id
+                    members = list(self._members.values())
+                    conns = list(self._conns)
+                # fan out announce to every connected executor
+                # (reference :89-112)
+                payload = rpc.pack_announce(self.app_id, members)
+                for c in conns:
+                    try:
+                        c.send(rpc.MSG_ANNOUNCE, payload)
+                    except OSError:
+                        pass
         elif mtype == rpc.MSG_REGISTER:
             _, num_maps, num_partitions = rpc.unpack_register(body)
             meta = self._register_shuffle(num_maps, num_partitions)

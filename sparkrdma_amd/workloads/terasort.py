@@ -236,6 +236,9 @@ class TeraSort:
                 self._validate(outs[-1], chunk_lo, per)
         eng.unregister_shuffle(handle)
         dt = time.perf_counter() - t0
+        # the step's sorted chunks, for callers that inspect the output
+        # (views of the reused sort buffers: valid until the next step)
+        self.last_outputs = outs
         return TeraSortResult(
             seconds=dt, records=self.n,
             bytes_sorted=self.n * self.RECORD_BYTES,

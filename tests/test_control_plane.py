@@ -154,6 +154,54 @@ def test_late_joining_executor_announced_to_all(pair, tmp_path):
         late.stop()
 
 
+def test_concurrent_joins_converge_on_full_membership(tmp_path, monkeypatch):
+    """Executors keep the LAST membership they are sent, so the driver must
+    never deliver an older snapshot after a newer one: each snapshot and
+    its fan-out happen under one lock, and executors joining at the same
+    moment all end up seeing everyone."""
+    import time
+    from sparkrdma_amd import rpc
+    conf = ShuffleConf(shm_dir=str(tmp_path), max_buffer_allocation_size=1 << 30)
+    driver = Driver(conf)
+    held = []
+    orig_send = rpc.MsgConnection.send
+
+    def send(self, mtype, body):
+        if mtype == rpc.MSG_ANNOUNCE:
+            held.append(driver._announce_lock.locked())
+        return orig_send(self, mtype, body)
+
+    monkeypatch.setattr(rpc.MsgConnection, "send", send)
+    N = 8
+    mgrs = [None] * N
+
+    def join(i):
+        mgrs[i] = ShuffleManager(
+            ShuffleConf(shm_dir=str(tmp_path),
+                        max_buffer_allocation_size=1 << 30),
+            executor_id=i, driver_port=driver.port)
+
+    threads = [threading.Thread(target=join, args=(i,)) for i in range(N)]
+    try:
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join()
+        assert all(m is not None for m in mgrs)
+        deadline = time.monotonic() + 10
+        while time.monotonic() < deadline and any(
+                len(m._members) < N for m in mgrs):
+            time.sleep(0.005)
+        for m in mgrs:
+            assert set(m._members) == set(range(N))
+        assert len(held) >= N and all(held)
+    finally:
+        for m in mgrs:
+            if m is not None:
+                m.stop()
+        driver.stop()
+
+
 def test_double_stop_idempotent(tmp_path):
     """stop() twice on every component is a no-op, not an error — teardown
     runs from finally blocks and signal handlers, so it must be safe to
