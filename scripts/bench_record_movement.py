@@ -1,0 +1,115 @@
+"""Micro-bench of the record-moving kernels on one MI355X.
+
+Run on a GPU box:  python scripts/bench_record_movement.py [--gb 4]
+Times, for 100-byte and 256-byte records:
+  * gather_records dst_mode 0 (records -> sorted output, random permutation)
+  * gather_records dst_mode 1 (records -> 256 per-digit destinations)
+  * sort_records(fuse=True)   (pair extract + radix passes + fused gather)
+with device events, median of --launches launches, at a size far past the
+256 MB Infinity Cache. GB/s counts each record's bytes ONCE (n * W / time):
+the kernels read and write every record once, so memory traffic is at
+least twice that figure.
+"""
+
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch
+
+from sparkrdma_amd.ops import load
+from sparkrdma_amd.ops.radix import sort_records
+
+
+def timed_ms(fn, launches, warmup=2):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(launches):
+        t0 = torch.cuda.Event(enable_timing=True)
+        t1 = torch.cuda.Event(enable_timing=True)
+        t0.record()
+        fn()
+        t1.record()
+        t1.synchronize()
+        ms.append(t0.elapsed_time(t1))
+    ms.sort()
+    return ms[len(ms) // 2]
+
+
+def report(name, W, n, ms):
+    print(f"W={W:4d} n={n:10d} {name:28s} {ms:9.3f} ms  "
+          f"{n * W / ms / 1e6:8.1f} GB/s of record bytes", flush=True)
+
+
+def bench_width(hs, W, total_bytes, launches):
+    n = (total_bytes // W) & ~1     # even: n * W is a whole number of u64
+    dev = "cuda"
+    s = torch.cuda.current_stream().cuda_stream
+    g = torch.Generator(device=dev)
+    g.manual_seed(W)
+    recs = torch.randint(-2**63, 2**63 - 1, (n * W // 8,), dtype=torch.int64,
+                         device=dev, generator=g).view(torch.uint8)
+    out = torch.empty(n * W, dtype=torch.uint8, device=dev)
+
+    # (key, aux) pairs: key = the record's own prefix, aux = random record
+    # index with key-low bits in the high 16 (masked off by the kernels)
+    perm = torch.randperm(n, device=dev, generator=g)
+    pairs = torch.empty(n, 2, dtype=torch.int64, device=dev)
+    keyw = recs.view(n, W)[:, :8].contiguous().view(torch.int64).view(n)
+    pairs[:, 0] = keyw[perm]
+    pairs[:, 1] = perm | (0x5A5A << 48)
+    del keyw
+    ms = timed_ms(lambda: hs.gather_records(
+        recs.data_ptr(), pairs.data_ptr(), n, W, 0, out.data_ptr(),
+        0, 0, 0, 0, 0, 0, s), launches)
+    report("gather_records mode 0", W, n, ms)
+
+    # mode 1: pairs grouped by the top 8 key bits, one destination per digit
+    digit = (pairs[:, 0] >> 56) & 255
+    order = torch.argsort(digit, stable=True)
+    grouped = pairs[order].contiguous()
+    counts = torch.bincount(digit, minlength=256)
+    del digit, order, perm, pairs
+    starts = torch.cumsum(counts, 0) - counts
+    dst_addr = out.data_ptr() + starts * W
+    dstart = starts.to(torch.int32)
+    ms = timed_ms(lambda: hs.gather_records(
+        recs.data_ptr(), grouped.data_ptr(), n, W, 1, 0,
+        dst_addr.data_ptr(), dstart.data_ptr(), 56, 255, 0, 0, s), launches)
+    report("gather_records mode 1", W, n, ms)
+    del grouped
+
+    prs = torch.empty(2 * n, dtype=torch.int64, device=dev)
+    tmp = torch.empty(2 * n, dtype=torch.int64, device=dev)
+    ms = timed_ms(lambda: sort_records(recs, W, key_bytes=10, out=out,
+                                       pairs=prs, tmp=tmp, fuse=True),
+                  launches)
+    report("sort_records(fuse=True)", W, n, ms)
+    ms = timed_ms(lambda: sort_records(recs, W, key_bytes=10, out=out,
+                                       pairs=prs, tmp=tmp, fuse=False),
+                  launches)
+    report("sort_records(fuse=False)", W, n, ms)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gb", type=float, default=4.0,
+                    help="record bytes per case (default 4 GB)")
+    ap.add_argument("--launches", type=int, default=11)
+    args = ap.parse_args()
+    if args.launches < 10:
+        ap.error("--launches must be at least 10")
+    if not torch.cuda.is_available():
+        sys.exit("bench_record_movement needs a GPU")
+    hs = load()
+    for W in (100, 256):
+        bench_width(hs, W, int(args.gb * 1e9), args.launches)
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()

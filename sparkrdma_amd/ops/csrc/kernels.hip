@@ -403,6 +403,80 @@ __global__ __launch_bounds__(BLOCK) void radix_scatter_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Batched record copy, shared by gather_records_kernel and the fused final
+// sort pass (see 'wide-record machinery' below). The caller stages one
+// (source, destination) address pair per record in LDS; the block then
+// moves the records one word per lane.
+
+constexpr uint64_t AUX_IDX_MASK = (1ull << 48) - 1;  // aux = keylo16<<48 | idx
+
+struct GatherSlot {
+  const uint32_t* src;  // first word of the record
+  uint32_t* dst;        // first word of its destination slot
+};
+
+// independent record loads a lane issues before its first store
+constexpr int GATHER_BATCH = 8;  // 16: no faster, 90 / 160 VGPRs
+
+// Copy nslots records of w4 words each. Word q of the block is word
+// q % w4 of slot q / w4, so a wave-instruction reads 256 consecutive bytes
+// of consecutive slots' records and its store is 256 contiguous bytes
+// within a destination run. (slot, word) advance by the block-uniform
+// step (BS / w4, BS % w4): one division per lane, none per word. Each
+// lane issues U loads before its first store, and the loop body is
+// branch-free so no wait separates the loads.
+//
+// Lane mapping: one dword per lane measured FASTER than 16 bytes per lane
+// with a narrower tail (100 B = 6 x 16 + 4) — 2.55 vs 4.5 ms for 4 GB of
+// 100-byte records, equal at 256 bytes where there is no tail; the tail
+// chunks are 4-byte accesses 100 bytes apart
+// (profiles/r03_record_movement.md).
+//
+// INVARIANT (no access outside the record): a lane touches word o of
+// slot r only with r < nslots and o < w4, on both sides, and every access
+// is exactly one word wide. So it lies inside [record, record + W) on the
+// source and inside the record's destination slot on the destination.
+template <int BS, int U>
+__device__ __forceinline__ void copy_record_words(const GatherSlot* slots,
+                                                  uint32_t nslots,
+                                                  uint32_t w4) {
+  // the addresses come out of LDS: name the global address space, else
+  // the accesses lower to flat_load / flat_store
+  typedef const __attribute__((address_space(1))) uint32_t* gsrc_t;
+  typedef __attribute__((address_space(1))) uint32_t* gdst_t;
+  const uint32_t total = nslots * w4;
+  const uint32_t dr = BS / w4, dc = BS % w4;
+  uint32_t r = threadIdx.x / w4, o = threadIdx.x % w4;
+#pragma unroll 1
+  for (uint32_t q0 = 0; q0 < total; q0 += BS * U) {
+    uint32_t v[U];
+    gdst_t dst[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      // lanes past the end re-read the block's last word (inside a
+      // record) and skip the store below
+      const bool ok = q0 + (uint32_t)u * BS + threadIdx.x < total;
+      const GatherSlot s = slots[ok ? r : nslots - 1];
+      const uint32_t w = ok ? o : w4 - 1;
+      v[u] = ((gsrc_t)s.src)[w];
+      dst[u] = (gdst_t)s.dst + w;
+      o += dc;
+      r += dr;
+      if (o >= w4) {
+        o -= w4;
+        ++r;
+      }
+    }
+    // plain cached accesses: streaming (nontemporal) hints measured
+    // 252 vs 256 GB/s on the flagship — the L2 reuse between the
+    // producing kernels and the copy outweighs the pollution
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (q0 + (uint32_t)u * BS + threadIdx.x < total) *dst[u] = v[u];
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Onesweep path (8-bit digits): one kernel per pass with decoupled
 // lookback — removes the per-pass hist read and the scan kernels.
 //
@@ -759,20 +833,27 @@ __attribute__((amdgpu_waves_per_eu(LEAN ? 6 : 1))) void onesweep_pass_kernel(
       if (round == 0) t3 = timing ? __builtin_amdgcn_s_memrealtime() : 0;
       if (FUSE_GATHER) {
         // copy each slot's RECORD to its final position: key_dst[d]
-        // holds per-digit record bases; word-mapped like gather_records
-        // (writes coalesce within digit runs, reads are the random
-        // per-record chunks the separate gather paid anyway)
-        const uint32_t total_w = tile_n * rec_w4;
-        for (uint32_t w = tid; w < total_w; w += BS) {
-          uint32_t j = w / rec_w4, o = w - j * rec_w4;
+        // holds per-digit record bases. Each slot's pair is replaced IN
+        // PLACE by its (record source, destination) addresses — digit,
+        // offset and index derived once per slot — then the block runs
+        // the same batched word copy as gather_records (writes coalesce
+        // within digit runs, reads are the random per-record chunks the
+        // separate gather paid anyway). Block-uniform code: FUSE_GATHER
+        // runs a single round and every thread reaches the barrier.
+        GatherSlot* slots = reinterpret_cast<GatherSlot*>(smem_raw);
+        for (uint32_t j = tid; j < tile_n; j += BS) {
           u64x2 kv = exch2[j];
           uint32_t d = (uint32_t)((uint64_t)(sort_word ? kv.y : kv.x)
                                   >> shift) & (ND - 1);
           uint32_t off = (pref[d] + (j - start[d])) & off_mask;
-          uint64_t idx = (uint64_t)kv.y & ((1ull << 48) - 1);
-          reinterpret_cast<uint32_t*>(key_dst[d])[(uint64_t)off * rec_w4 + o] =
-              rec_words[idx * rec_w4 + o];
+          uint64_t idx = (uint64_t)kv.y & AUX_IDX_MASK;
+          slots[j] = GatherSlot{
+              rec_words + idx * rec_w4,
+              reinterpret_cast<uint32_t*>(key_dst[d]) +
+                  (uint64_t)off * rec_w4};
         }
+        __syncthreads();
+        copy_record_words<BS, GATHER_BATCH>(slots, tile_n, rec_w4);
       } else {
 #pragma unroll
       for (int i = 0; i < IT; ++i) {
@@ -923,24 +1004,36 @@ __global__ __launch_bounds__(BLOCK) void extract_pairs_kernel(
 //   dst_mode 0: out_base + j*rec_bytes                  (sorted output)
 //   dst_mode 1: dst_addr[d] + (j - dstart[d])*rec_bytes (partition path,
 //               d = digit_of(pairs[2j]) — per-digit HBM block positions)
-constexpr uint64_t AUX_IDX_MASK = (1ull << 48) - 1;
+//
+// The copy is latency-bound unless many record bytes are in flight per
+// CU (random ~100-byte reads from a buffer far past the Infinity Cache),
+// so the block first stages every record's (source, destination) address
+// pair in LDS from coalesced 16-byte pair loads — no global load sits in
+// front of a record load, and index / digit / destination are derived
+// once per record — and then copies in batches: GATHER_BATCH independent
+// loads per lane are issued before the first dependent store.
+// In flight per CU = resident lanes x GATHER_BATCH x 4 B: 64 KB for the
+// stand-alone gather at 8 blocks/CU (48 VGPRs), 32 KB for the fused sort
+// pass at 2 x 512 threads. A 16-deep batch measured no faster in either
+// kernel and costs the fused pass its second resident block (160 VGPRs)
+// — profiles/r03_record_movement.md.
+constexpr uint32_t GATHER_MAX_RECS = 1024;  // per block: 16 KB of LDS slots
 
 __global__ __launch_bounds__(BLOCK) void gather_records_kernel(
     const uint32_t* __restrict__ recs, const uint64_t* __restrict__ pairs,
-    uint64_t n, uint32_t w4 /* rec_bytes/4 */, uint32_t recs_per_block,
-    int dst_mode, uint64_t out_base,
-    const uint64_t* __restrict__ dst_addr,
+    uint64_t n, uint32_t w4 /* rec_bytes/4 */,
+    uint32_t recs_per_block /* <= GATHER_MAX_RECS */, int dst_mode,
+    uint64_t out_base, const uint64_t* __restrict__ dst_addr,
     const uint32_t* __restrict__ dstart, int shift, uint32_t mask,
     int func, uint32_t nparts) {
+  __shared__ GatherSlot slots[GATHER_MAX_RECS];
   const uint64_t r0 = (uint64_t)blockIdx.x * recs_per_block;
   if (r0 >= n) return;
   const uint32_t nr = (uint32_t)min((uint64_t)recs_per_block, n - r0);
-  const uint32_t total = nr * w4;
-  for (uint32_t w = threadIdx.x; w < total; w += BLOCK) {
-    uint32_t r = w / w4, o = w - r * w4;
-    uint64_t j = r0 + r;
+  for (uint32_t r = threadIdx.x; r < nr; r += BLOCK) {
+    const uint64_t j = r0 + r;
     ulonglong2 pr = reinterpret_cast<const ulonglong2*>(pairs)[j];
-    uint64_t idx = pr.y & AUX_IDX_MASK;
+    const uint64_t idx = pr.y & AUX_IDX_MASK;
     uint32_t* dst;
     if (dst_mode == 0) {
       dst = reinterpret_cast<uint32_t*>(out_base) + j * w4;
@@ -949,11 +1042,10 @@ __global__ __launch_bounds__(BLOCK) void gather_records_kernel(
       dst = reinterpret_cast<uint32_t*>(dst_addr[d]) +
             (uint64_t)(uint32_t)(j - dstart[d]) * w4;
     }
-    // plain cached accesses: streaming (nontemporal) hints measured
-    // 252 vs 256 GB/s on the flagship — the L2 reuse between the
-    // producing kernels and this gather outweighs the pollution
-    dst[o] = recs[idx * w4 + o];
+    slots[r] = GatherSlot{recs + idx * w4, dst};
   }
+  __syncthreads();
+  copy_record_words<BLOCK, GATHER_BATCH>(slots, nr, w4);
 }
 
 void extract_pairs(uintptr_t recs, uint64_t n, uint32_t rec_bytes,
@@ -986,7 +1078,10 @@ void gather_records(uintptr_t recs, uintptr_t pairs, uint64_t n,
   if (rec_bytes % 4) throw std::runtime_error("rec_bytes % 4 != 0");
   auto s = reinterpret_cast<hipStream_t>(stream);
   uint32_t w4 = rec_bytes / 4;
-  uint32_t rpb = 16384 / w4;           // ~16k words per block
+  // ~32k words per block (whole copy batches at W = 100 and 256), at
+  // most GATHER_MAX_RECS records (the kernel's LDS slot table)
+  uint32_t rpb = 32768 / w4;
+  if (rpb > GATHER_MAX_RECS) rpb = GATHER_MAX_RECS;
   if (rpb < 1) rpb = 1;
   uint64_t grid = (n + rpb - 1) / rpb;
   if (grid > 0x7FFFFFFF) throw std::runtime_error("grid too large");
@@ -1382,8 +1477,11 @@ static int onesweep_sort_tmpl(uintptr_t keys, uintptr_t vals,
     if (sb > 64 - PBITS) sb = 64 - PBITS;  // same clamp as hist_all
     // fused final pass: the writeout copies whole records to fuse_out
     // (the gather folded into the sort — key_dst becomes record bases)
+    // (not in hist+scan mode: the fused kernel walks lookback descriptors,
+    // which that mode never resets — the caller falls back via -1)
     const bool fuse = fuse_recs && p == passes - 1 && aos &&
-                      aos_tile == 4096 && g_split_exch <= 1 && !g_lean;
+                      aos_tile == 4096 && g_split_exch <= 1 && !g_lean &&
+                      !want_hist;
     if (use_hist) {
       hist_launch<PBITS>(reinterpret_cast<const uint64_t*>(src_k), n, sb,
                          hist32, s, 0, 2);
