@@ -5,6 +5,8 @@ Times, for 100-byte and 256-byte records:
   * gather_records dst_mode 0 (records -> sorted output, random permutation)
   * gather_records dst_mode 1 (records -> 256 per-digit destinations)
   * sort_records(fuse=True)   (pair extract + radix passes + fused gather)
+  * sort_records with the tie repair on and off, on random keys and on
+    all-equal keys (the input that forces the fallback to the full passes)
 with device events, median of --launches launches, at a size far past the
 256 MB Infinity Cache. GB/s counts each record's bytes ONCE (n * W / time):
 the kernels read and write every record once, so memory traffic is at
@@ -93,6 +95,31 @@ def bench_width(hs, W, total_bytes, launches):
                                        pairs=prs, tmp=tmp, fuse=False),
                   launches)
     report("sort_records(fuse=False)", W, n, ms)
+
+    # truncated sort + tie repair against the full LSD sequence, on random
+    # keys (path 1) and on all-equal keys, which force the fallback (path
+    # 2: truncated attempt, then the full sequence). A build without the
+    # switch times its only path.
+    def sort_case(name, mode):
+        if hasattr(hs, "set_tie_repair"):
+            hs.set_tie_repair(mode)
+        elif mode == 0:
+            return
+        try:
+            ms = timed_ms(lambda: sort_records(recs, W, key_bytes=10,
+                                               out=out, pairs=prs, tmp=tmp),
+                          launches)
+        finally:
+            if hasattr(hs, "set_tie_repair"):
+                hs.set_tie_repair(1)
+        path = hs.last_sort_path() if hasattr(hs, "last_sort_path") else 0
+        report(f"{name} repair={mode} path={path}", W, n, ms)
+
+    sort_case("sort random", 1)
+    sort_case("sort random", 0)
+    recs.view(n, W)[:, :10] = 0x5A
+    sort_case("sort equal keys", 1)
+    sort_case("sort equal keys", 0)
 
 
 def main():

@@ -108,6 +108,23 @@ PYBIND11_MODULE(_hipshuffle, m) {
   m.def("set_lookback_mode", &hs::set_lookback_mode);
   m.def("set_split_exchange", &hs::set_split_exchange);
   m.def("set_lean_pass", &hs::set_lean_pass);
+  m.def("set_tie_repair", &hs::set_tie_repair);
+  m.def("last_sort_path", &hs::last_sort_path);
+  m.def("tie_repair_tile", &hs::tie_repair_tile);
+  m.def("tie_repair_max_run", &hs::tie_repair_max_run);
+  m.def("sort_records_plan",
+        [](uint32_t n, int end_bit) {
+          int lo_bit, passes, run_bits;
+          hs::sort_records_plan(n, end_bit, &lo_bit, &passes, &run_bits);
+          return py::make_tuple(lo_bit, passes, run_bits);
+        },
+        py::arg("n"), py::arg("end_bit") = 64);
+  m.def("sort_records_truncated_u64", &hs::sort_records_truncated_u64,
+        py::arg("pairs"), py::arg("tmp_pairs"), py::arg("n"),
+        py::arg("end_bit"), py::arg("key_bytes"), py::arg("ws"),
+        py::arg("stream"), py::arg("recs"), py::arg("out"),
+        py::arg("rec_bytes"), py::arg("fuse") = 1,
+        py::call_guard<py::gil_scoped_release>());
   m.def("onesweep_sort_aos7_u64", &hs::onesweep_sort_aos7_u64,
         py::arg("pairs"), py::arg("tmp_pairs"), py::arg("n"),
         py::arg("start_bit"), py::arg("end_bit"), py::arg("ws"),

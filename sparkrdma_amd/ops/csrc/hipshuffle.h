@@ -88,6 +88,18 @@ int onesweep_sort_aos_fused_u64(uintptr_t pairs, uintptr_t tmp_pairs,
                                 uintptr_t ws, uintptr_t stream,
                                 int sort_word, uintptr_t recs,
                                 uintptr_t out, uint32_t rec_bytes);
+// truncated wide-record sort with tie repair (kernels.hip)
+void set_tie_repair(int m);
+int last_sort_path();
+int tie_repair_tile();
+int tie_repair_max_run();
+void sort_records_plan(uint32_t n, int end_bit, int* lo_bit, int* passes,
+                       int* run_bits);
+int sort_records_truncated_u64(uintptr_t pairs, uintptr_t tmp_pairs,
+                               uint32_t n, int end_bit, int key_bytes,
+                               uintptr_t ws, uintptr_t stream,
+                               uintptr_t recs, uintptr_t out,
+                               uint32_t rec_bytes, int fuse);
 int onesweep_sort_pairs_u64(uintptr_t keys, uintptr_t vals,
                             uintptr_t tmp_keys, uintptr_t tmp_vals,
                             uint32_t n, int start_bit, int end_bit,

@@ -1097,6 +1097,104 @@ void gather_records(uintptr_t recs, uintptr_t pairs, uint64_t n,
 }
 
 // ---------------------------------------------------------------------------
+// Tie repair for the truncated wide-record sort (sort_records_truncated_u64
+// below). The pairs arrive stably ordered by the RUN BITS only — prefix
+// bits [lo_bit, top), selected by run_mask — so elements that agree on
+// them are adjacent and in input order. With 2^run_bits >= 8n such runs
+// are rare and short for non-degenerate keys, and ordering each of them
+// by (prefix & lo_mask, aux) as one 128-bit value gives exactly what the
+// skipped low LSD passes would have: aux = keylo16 << 48 | idx, so that
+// order IS the remaining key bits with ties broken by input index. Bits
+// at and above `top` are deliberately ignored — the stable final pass
+// sorts by them afterwards.
+//
+// A run belongs to the block whose own tile holds its first element; the
+// owner insertion-sorts runs of 2..TIE_L elements in LDS (one thread per
+// run, runs are disjoint) and writes back only runs it changed. A run
+// longer than TIE_L is left alone and reported through *flag, and the host
+// then falls back to the full LSD sequence. No cross-block communication.
+constexpr int TIE_BS = 256;
+constexpr int TIE_IT = 8;
+constexpr int TIE_TILE = TIE_BS * TIE_IT;  // 2048 pairs, 32 KB of LDS
+constexpr int TIE_L = 32;                  // longest run repaired in place
+
+__global__ __launch_bounds__(TIE_BS) void tie_repair_kernel(
+    uint64_t* pairs, uint32_t n, uint64_t run_mask, uint64_t lo_mask,
+    uint32_t* __restrict__ flag) {
+  using u64x2 = __attribute__((ext_vector_type(2))) unsigned long long;
+  // sh[j] = element base + j: the tile, then TIE_L halo elements — the
+  // TIE_L - 1 a run starting at the tile's last element may cover, plus
+  // the one whose run bits tell whether that run is longer still
+  __shared__ u64x2 sh[TIE_TILE + TIE_L];
+  __shared__ uint64_t pred_sh;
+  u64x2* g = reinterpret_cast<u64x2*>(pairs);
+  const int tid = threadIdx.x;
+  const uint64_t base = (uint64_t)blockIdx.x * TIE_TILE;
+  const uint32_t avail =  // elements of sh that exist (base < n always)
+      (uint32_t)min((uint64_t)(TIE_TILE + TIE_L), (uint64_t)n - base);
+  const uint32_t tile_n = min(avail, (uint32_t)TIE_TILE);
+  // IN PLACE: the predecessor and the halo belong to neighbouring blocks,
+  // which may be rewriting them while they are read here. That is benign
+  // only because every value that can ever stand in such a slot is a
+  // member of the same run, i.e. has the same run bits, and run bits are
+  // all this block ever uses of an element it does not own (halo elements
+  // of a run that STARTS in this tile are owned here and written by no
+  // one else).
+  if (tile_n == TIE_TILE) {  // full tile: all loads issued before any use
+    u64x2 v[TIE_IT];
+#pragma unroll
+    for (int k = 0; k < TIE_IT; ++k) v[k] = g[base + k * TIE_BS + tid];
+#pragma unroll
+    for (int k = 0; k < TIE_IT; ++k) sh[k * TIE_BS + tid] = v[k];
+    if (tid < TIE_L && TIE_TILE + tid < avail)
+      sh[TIE_TILE + tid] = g[base + TIE_TILE + tid];
+  } else {
+    for (uint32_t j = tid; j < tile_n; j += TIE_BS) sh[j] = g[base + j];
+  }
+  if (tid == TIE_L && base > 0) pred_sh = pairs[2 * (base - 1)];
+  __syncthreads();
+
+#pragma unroll 1
+  for (uint32_t i = tid; i < tile_n; i += TIE_BS) {
+    const uint64_t k = sh[i].x;
+    const bool start =
+        i ? ((sh[i - 1].x ^ k) & run_mask) != 0
+          : (base == 0 || ((pred_sh ^ k) & run_mask) != 0);
+    if (!start || i + 1 >= avail || ((sh[i + 1].x ^ k) & run_mask)) continue;
+    // a run of >= 2 starts here; i + TIE_L < TILE + TIE_L bounds the scan
+    const uint32_t lim = min(avail - i, (uint32_t)TIE_L + 1);
+    uint32_t len = 2;
+#pragma unroll 1
+    while (len < lim && ((sh[i + len].x ^ k) & run_mask) == 0) ++len;
+    if (len > TIE_L) {
+      atomicOr(flag, 1u);
+      continue;
+    }
+    bool changed = false;
+#pragma unroll 1
+    for (uint32_t a = 1; a < len; ++a) {
+      const u64x2 x = sh[i + a];
+      const uint64_t xk = x.x & lo_mask;
+      uint32_t b = a;
+      while (b > 0) {
+        const u64x2 u = sh[i + b - 1];
+        const uint64_t uk = u.x & lo_mask;
+        if (uk < xk || (uk == xk && u.y <= x.y)) break;
+        sh[i + b] = u;
+        --b;
+      }
+      if (b != a) {
+        sh[i + b] = x;
+        changed = true;
+      }
+    }
+    if (changed)
+#pragma unroll 1
+      for (uint32_t a = 0; a < len; ++a) g[base + i + a] = sh[i + a];
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Microbench probe: emulate the scatter's write pattern — each block
 // writes its tile as `nregions` bursts of `burst` bytes at region-strided
 // scattered offsets. Measures HBM efficiency vs burst length to size the
@@ -1417,7 +1515,10 @@ static int onesweep_sort_tmpl(uintptr_t keys, uintptr_t vals,
                               uintptr_t ws, hipStream_t s, int aos,
                               int sort_word = 0, uintptr_t fuse_recs = 0,
                               uintptr_t fuse_out = 0,
-                              uint32_t fuse_rec_bytes = 0) {
+                              uint32_t fuse_rec_bytes = 0,
+                              uint64_t tie_run_mask = 0,
+                              uint64_t tie_lo_mask = 0,
+                              uint32_t* tie_flag = nullptr) {
   constexpr int PD = 1 << PBITS;
   const int aos_tile = g_aos_tile;
   uint32_t nb = aos ? os_num_tiles_t(n, aos_tile) : os_num_tiles(n);
@@ -1500,6 +1601,15 @@ static int onesweep_sort_tmpl(uintptr_t keys, uintptr_t vals,
     }
     const uint32_t* pass_pref = use_hist ? hist32 : nullptr;
     if (fuse) {   // (ticket/desc were reset in the !use_hist block)
+      if (tie_flag) {
+        // truncated sort: the passes so far ordered the pairs by the run
+        // bits only; put the tied runs in order before the final digit
+        hipLaunchKernelGGL(tie_repair_kernel,
+                           dim3(os_num_tiles_t(n, TIE_TILE)), dim3(TIE_BS),
+                           0, s, reinterpret_cast<uint64_t*>(src_k), n,
+                           tie_run_mask, tie_lo_mask, tie_flag);
+        HIP_CHECK(hipGetLastError());
+      }
       hipLaunchKernelGGL(
           (onesweep_pass_kernel<true, 8, true, 512, PBITS, false, true>),
           dim3(nb), dim3(512), lds, s,
@@ -1602,6 +1712,93 @@ int onesweep_sort_aos_fused_u64(uintptr_t pairs, uintptr_t tmp_pairs,
   return onesweep_sort_tmpl<8>(pairs, 0, tmp_pairs, 0, n, start_bit, end_bit,
                                ws, reinterpret_cast<hipStream_t>(stream), 1,
                                sort_word, recs, out, rec_bytes);
+}
+
+// ---------------------------------------------------------------------------
+// Truncated wide-record sort. After the records are ordered by any
+// run_bits consecutive key bits with 2^run_bits >= 8n, a record of a
+// non-degenerate input shares those bits with < 1/8 other records on
+// average, so LSD passes over the bits below them sort almost nothing.
+// Instead: LSD over prefix bits [lo_bit, top) only, tie_repair_kernel on
+// the rare tied runs, then the unchanged fused final pass over
+// [top, end_bit). Inputs with a run longer than TIE_L fall back to the
+// full sequence, so the output never depends on the path taken.
+
+// 0 = always the full LSD sequence; m >= 1 = truncated sort with tie
+// repair, using 8 * (m - 1) run bits more than the 8n rule (A/B knob)
+static int g_tie_repair = 1;
+void set_tie_repair(int m) { g_tie_repair = m < 0 ? 0 : m; }
+// path of the latest sort_records_truncated_u64 call: 0 = full sequence
+// only (by the caller), 1 = truncated, 2 = truncated then full fallback
+static int g_last_sort_path = 0;
+int last_sort_path() { return g_last_sort_path; }
+int tie_repair_tile() { return TIE_TILE; }
+int tie_repair_max_run() { return TIE_L; }
+
+// Digits count DOWN from end_bit so every pass covers 8 live bits: the
+// final (fused) digit starts at top = end_bit - 8, the run bits are the
+// run_bits below it. passes == 0: the truncated plan does not apply (it
+// would leave fewer than 8 low prefix bits, saving under two passes).
+void sort_records_plan(uint32_t n, int end_bit, int* lo_bit, int* passes,
+                       int* run_bits) {
+  if (end_bit > 64) end_bit = 64;
+  int rb = 8;
+  while (rb < 64 && (1ull << rb) < 8ull * n) rb += 8;
+  rb += 8 * (g_tie_repair > 1 ? g_tie_repair - 1 : 0);
+  *run_bits = rb;
+  *lo_bit = end_bit - 8 - rb;
+  *passes = *lo_bit >= 8 ? rb / 8 + 1 : 0;
+}
+
+// Sorts the extracted pairs and writes the sorted RECORDS to `out`.
+// Returns the path taken (1 or 2), or -1 having done nothing when the
+// truncated sort is bypassed — `fuse` off, tie repair off, no plan, or
+// any ablation global under which the fused final pass does not apply —
+// and the caller runs the full sequence itself. ws must be sized for the
+// full sequence (ceil(end_bit / 8) + 2 aux passes): the overflow flag
+// lives in the totals rows the shorter plan leaves unused.
+// BLOCKS on the stream once (the flag decides whether to fall back).
+int sort_records_truncated_u64(uintptr_t pairs, uintptr_t tmp_pairs,
+                               uint32_t n, int end_bit, int key_bytes,
+                               uintptr_t ws, uintptr_t stream,
+                               uintptr_t recs, uintptr_t out,
+                               uint32_t rec_bytes, int fuse) {
+  g_last_sort_path = 0;
+  if (end_bit > 64) end_bit = 64;
+  if (!fuse || !g_tie_repair || n == 0 || g_aos_tile != 4096 ||
+      g_split_exch > 1 || g_lean || g_sort_mode != 0)
+    return -1;
+  int lo_bit, passes, run_bits;
+  sort_records_plan(n, end_bit, &lo_bit, &passes, &run_bits);
+  if (passes == 0) return -1;
+  auto s = reinterpret_cast<hipStream_t>(stream);
+  const int top = end_bit - 8;
+  const uint64_t lo_mask = (1ull << lo_bit) - 1;
+  const uint64_t run_mask = ((1ull << top) - 1) & ~lo_mask;
+  // first bytes past what a `passes`-pass sort lays out in ws
+  uint32_t* flag = reinterpret_cast<uint32_t*>(
+      ws + onesweep_workspace_bytes(n, passes));
+  HIP_CHECK(hipMemsetAsync(flag, 0, 4, s));
+  int cur = onesweep_sort_tmpl<8>(pairs, 0, tmp_pairs, 0, n, lo_bit, end_bit,
+                                  ws, s, 1, 0, recs, out, rec_bytes,
+                                  run_mask, lo_mask, flag);
+  if (cur < 0) throw std::runtime_error("truncated sort: fusion refused");
+  uint32_t overflow = 0;
+  HIP_CHECK(hipMemcpyAsync(&overflow, flag, 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  if (!overflow) return g_last_sort_path = 1;
+  // some run was too long to repair: the full sequence on the pairs as
+  // they now stand. Every step so far was stable, so equal full keys are
+  // still in input order and the LSD sort gives today's output; `out` is
+  // simply overwritten.
+  if (cur == 1) std::swap(pairs, tmp_pairs);
+  if (key_bytes > 8 &&
+      onesweep_sort_tmpl<8>(pairs, 0, tmp_pairs, 0, n, 48, 64, ws, s, 1, 1))
+    std::swap(pairs, tmp_pairs);
+  if (onesweep_sort_tmpl<8>(pairs, 0, tmp_pairs, 0, n, 0, end_bit, ws, s, 1,
+                            0, recs, out, rec_bytes) < 0)
+    throw std::runtime_error("sort fallback: fusion refused");
+  return g_last_sort_path = 2;
 }
 
 int onesweep_sort_aos7_u64(uintptr_t pairs, uintptr_t tmp_pairs, uint32_t n,

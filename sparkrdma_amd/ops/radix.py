@@ -178,6 +178,11 @@ def sort_records(recs: torch.Tensor, rec_bytes: int, key_bytes: int = 8,
     gather pass then moves each record once — pair passes cost 16% of
     full-record passes at W = 100 (kernels.hip 'wide-record machinery').
     Returns the sorted records (a fresh tensor, or ``out``).
+
+    With ``fuse`` and the default kernel configuration the call BLOCKS on
+    the current stream once: the truncated sort reads back a flag that
+    says whether the full pass sequence must run after all. ``ws``, when
+    given, must be sized for the full sequence (as computed below).
     """
     m = load()
     n = recs.numel() // rec_bytes
@@ -203,6 +208,21 @@ def sort_records(recs: torch.Tensor, rec_bytes: int, key_bytes: int = 8,
     else:
         assert ws.numel() >= need_ws
     cur, other = prs, tmp
+    if out is None:
+        out = torch.empty_like(recs)
+    else:
+        assert out.numel() >= recs.numel()
+        out = out[:recs.numel()]
+    # truncated sort (kernels.hip sort_records_truncated_u64): LSD over the
+    # leading key bits only, tied runs repaired in LDS, full sequence as
+    # the fallback for inputs with long runs. -1 = bypassed (fuse off, tie
+    # repair off, no plan for this n/end_bit, or an ablation global set):
+    # nothing ran, take the full sequence below. Path: last_sort_path().
+    if m.sort_records_truncated_u64(
+            cur.data_ptr(), other.data_ptr(), n, min(end_bit, 64),
+            key_bytes, ws.data_ptr(), _stream(), recs.data_ptr(),
+            out.data_ptr(), rec_bytes, int(fuse)) != -1:
+        return out
     if key_bytes > 8:
         # LSD over the 80-bit key: 16 aux bits first, then the prefix
         r = m.onesweep_sort_aos_word_u64(cur.data_ptr(), other.data_ptr(),
@@ -210,11 +230,6 @@ def sort_records(recs: torch.Tensor, rec_bytes: int, key_bytes: int = 8,
                                          _stream(), 1)
         if r == 1:
             cur, other = other, cur
-    if out is None:
-        out = torch.empty_like(recs)
-    else:
-        assert out.numel() >= recs.numel()
-        out = out[:recs.numel()]
     if fuse:
         # the FINAL prefix pass writes whole records (kernels.hip
         # FUSE_GATHER): the last pair writeout + the separate gather's
