@@ -86,7 +86,24 @@ def main():
         eng.unregister_shuffle(handle)
         print(f"range-partitioned: keys per partition = {sizes}")
 
-        # 4) metrics: the task/executor counters the reference feeds Spark
+        # 4) reduceByKey with map-side combine ---------------------------
+        # stop(combiner=...) ships one row per distinct key of the map
+        # task; the reader merges those partial results
+        handle = eng.register_shuffle(num_maps=1, num_partitions=4)
+        writer = mgr.get_writer(handle, map_id=0)
+        k = rng.integers(0, 100, 50_000, dtype=np.uint64)
+        ones = np.ones(50_000, dtype=np.uint64)
+        writer.write_batch(k, ones.view(np.uint8).reshape(-1, 8))
+        writer.stop(True, partitioner=HashPartitioner(4), combiner="sum")
+        reader = mgr.get_reader(handle, 0, 3)
+        uk, sums = reader.read_aos(aggregator="sum", map_side_combined=True)
+        assert int(np.sum(sums)) == 50_000 and len(uk) == 100
+        shipped = writer.metrics.records_written
+        eng.unregister_shuffle(handle)
+        print(f"map-side combine: 50000 rows in, {shipped} rows shipped, "
+              f"{len(uk)} keys out")
+
+        # 5) metrics: the task/executor counters the reference feeds Spark
         print("lifetime:", mgr.lifetime_metrics.format())
 
 

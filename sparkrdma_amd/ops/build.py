@@ -23,7 +23,7 @@ def ext_path() -> str:
 
 def sources():
     return [os.path.join(CSRC, f) for f in ("pool.cpp", "kernels.hip",
-                                            "bindings.cpp")]
+                                            "reduce.hip", "bindings.cpp")]
 
 
 def needs_build() -> bool:

@@ -138,4 +138,11 @@ PYBIND11_MODULE(_hipshuffle, m) {
         py::arg("tmp_vals"), py::arg("n"), py::arg("start_bit"),
         py::arg("end_bit"), py::arg("ws"), py::arg("stream") = 0,
         py::call_guard<py::gil_scoped_release>());
+  m.def("reduce_by_key_tile", &hs::reduce_by_key_tile);
+  m.def("reduce_by_key_workspace_bytes", &hs::reduce_by_key_workspace_bytes);
+  m.def("reduce_by_key_count", &hs::reduce_by_key_count, py::arg("pairs"),
+        py::arg("n"), py::arg("op"), py::arg("ws"), py::arg("stream") = 0);
+  m.def("reduce_by_key_emit", &hs::reduce_by_key_emit, py::arg("pairs"),
+        py::arg("n"), py::arg("op"), py::arg("ws"), py::arg("out_keys"),
+        py::arg("out_vals"), py::arg("stream") = 0);
 }

@@ -105,4 +105,17 @@ int onesweep_sort_pairs_u64(uintptr_t keys, uintptr_t vals,
                             uint32_t n, int start_bit, int end_bit,
                             uintptr_t ws, uintptr_t stream);
 
+// reduce.hip — segmented reduce over key-sorted AoS (key, value) pairs.
+// op: 0 sum (i64, wraps), 1 sum_f64, 2 count, 3 min (i64), 4 max (i64).
+// Workspace: [lead u64 x nb][base u64 x nb][heads u32 x nb] for
+// nb = ceil(n / tile); the caller writes base[] = exclusive scan of heads[]
+// between the count and the emit call, and sizes out_* from its total.
+int reduce_by_key_tile();
+size_t reduce_by_key_workspace_bytes(uint32_t n);
+void reduce_by_key_count(uintptr_t pairs, uint32_t n, int op, uintptr_t ws,
+                         uintptr_t stream);
+void reduce_by_key_emit(uintptr_t pairs, uint32_t n, int op, uintptr_t ws,
+                        uintptr_t out_keys, uintptr_t out_vals,
+                        uintptr_t stream);
+
 }  // namespace hipshuffle

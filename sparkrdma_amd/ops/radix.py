@@ -12,6 +12,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import load
+# op names of reduce_by_key_aos; an op's index is its kernel op code
+from ..aggregate import AGGREGATORS as REDUCE_OPS
 
 
 def _stream() -> int:
@@ -144,6 +146,65 @@ def sort_pairs_aos(pairs: torch.Tensor, start_bit: int = 0,
     res = fn(pairs.data_ptr(), tmp.data_ptr(), n, start_bit,
              start_bit + bits, ws.data_ptr(), _stream())
     return pairs if res == 0 else tmp
+
+
+def reduce_by_key_aos(pairs: torch.Tensor, op: str,
+                      out_keys: Optional[torch.Tensor] = None,
+                      out_vals: Optional[torch.Tensor] = None,
+                      ws: Optional[torch.Tensor] = None
+                      ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Segmented reduce over interleaved (key u64, val u64) records whose
+    equal keys are adjacent (reduce.hip). ``pairs`` is an int64 tensor of
+    2n elements and is left unchanged. Returns SoA (keys, vals), one row
+    per run of equal keys in input order; ``vals`` is int64 (sum wraps,
+    min/max are signed, count is the run length), float64 for "sum_f64".
+    The summation order is fixed, so "sum_f64" is bit-reproducible.
+
+    BLOCKS on the current stream once, to read back the number of runs g.
+    ``out_keys``/``out_vals`` (int64, >= g elements) and ``ws`` (uint8,
+    >= reduce_by_key_workspace_bytes(n)) may be supplied by the caller; a
+    too-small output raises ValueError before anything is written to it.
+    """
+    if op not in REDUCE_OPS:
+        raise ValueError(f"unknown reduce op {op!r}; "
+                         f"expected one of {REDUCE_OPS}")
+    code = REDUCE_OPS.index(op)
+    n = pairs.numel() // 2
+    dev = pairs.device
+    if n == 0:
+        return (torch.empty(0, dtype=torch.int64, device=dev),
+                torch.empty(0, dtype=torch.int64, device=dev))
+    if n >= 1 << 32:
+        raise ValueError("reduce_by_key_aos handles n < 2^32 records")
+    m = load()
+    nb = -(-n // m.reduce_by_key_tile())
+    need_ws = m.reduce_by_key_workspace_bytes(n)
+    if ws is None:
+        ws = torch.empty(need_ws, dtype=torch.uint8, device=dev)
+    elif ws.numel() < need_ws:
+        raise ValueError(f"ws too small: {ws.numel()} < {need_ws} bytes")
+    s = _stream()
+    m.reduce_by_key_count(pairs.data_ptr(), n, code, ws.data_ptr(), s)
+    # workspace layout (hipshuffle.h): [lead u64 x nb][base u64 x nb]
+    # [heads u32 x nb]; the scan over nb tile counts is plumbing
+    heads = ws[16 * nb:20 * nb].view(torch.int32)
+    incl = torch.cumsum(heads, 0, dtype=torch.int64)
+    ws[8 * nb:16 * nb].view(torch.int64).copy_(incl - heads)
+    g = int(incl[-1])                       # syncs the stream
+    for name, t in (("out_keys", out_keys), ("out_vals", out_vals)):
+        if t is not None and t.numel() < g:
+            raise ValueError(f"{name} holds {t.numel()} elements, "
+                             f"the input has {g} runs")
+    if out_keys is None:
+        out_keys = torch.empty(g, dtype=torch.int64, device=dev)
+    if out_vals is None:
+        out_vals = torch.empty(g, dtype=torch.int64, device=dev)
+    m.reduce_by_key_emit(pairs.data_ptr(), n, code, ws.data_ptr(),
+                         out_keys.data_ptr(), out_vals.data_ptr(), s)
+    keys, vals = out_keys[:g], out_vals[:g]
+    if op == "sum_f64":
+        vals = vals.view(torch.float64)
+    return keys, vals
 
 
 def extract_pairs(recs: torch.Tensor, rec_bytes: int, key_bytes: int = 8,

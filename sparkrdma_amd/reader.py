@@ -524,7 +524,7 @@ class ShuffleReader:
     re-implementing it."""
 
     #: named reductions for read_aos(aggregator=...)
-    AGGREGATORS = ("sum", "sum_f64", "count", "min", "max")
+    from .aggregate import AGGREGATORS
 
     def __init__(self, manager: ShuffleManager, handle: ShuffleHandle,
                  start_partition: int, end_partition: int, arena=None):
@@ -565,7 +565,8 @@ class ShuffleReader:
 
     def read_aos(self, aggregator: Optional[str] = None,
                  ordering: bool = False, end_bit: int = 64,
-                 sort_tmp=None, sort_ws=None):
+                 sort_tmp=None, sort_ws=None,
+                 map_side_combined: bool = False):
         """Consume the whole partition range of AoS (u64 key, u64 value)
         records, applying an optional keyed reduction and/or key ordering
         ON DEVICE. Returns (keys, values):
@@ -576,10 +577,26 @@ class ShuffleReader:
         * aggregator in AGGREGATORS -> one row per distinct key, keys
           ascending; "sum_f64" treats the value payload as float64
         * both None/False -> unordered concatenated records
+
+        ``map_side_combined=True`` says the writers ran
+        ``stop(combiner=aggregator)``: the fetched rows are partial results
+        and are MERGED (the reference's combineCombinersByKey branch,
+        RdmaShuffleReader.scala:83-96) — "count" merges by summing the
+        per-map counts, every other aggregator merges with itself.
+
+        On the GPU lane the keyed reduction is the reduce_by_key kernel
+        (ops/csrc/reduce.hip): a fixed summation order, so "sum_f64" is
+        bit-reproducible.
         """
         if aggregator is not None and aggregator not in self.AGGREGATORS:
             raise ValueError(f"unknown aggregator {aggregator!r}; "
                              f"expected one of {self.AGGREGATORS}")
+        if map_side_combined:
+            if aggregator is None:
+                raise ValueError("map_side_combined=True needs the "
+                                 "aggregator the writers combined with")
+            from .aggregate import MERGE_OF
+            aggregator = MERGE_OF[aggregator]
         mgr = self.manager
         if mgr.gpu is not None:
             import torch
@@ -595,31 +612,10 @@ class ShuffleReader:
                 from .ops.radix import sort_pairs_aos
                 pairs = sort_pairs_aos(pairs, 0, end_bit, tmp=sort_tmp,
                                        ws=sort_ws)
-            k = pairs[0::2]
-            v = pairs[1::2]
             if aggregator is None:
-                return k, v
-            k = k.contiguous()
-            v = v.contiguous()
-            uk, inverse, cnt = torch.unique_consecutive(
-                k, return_inverse=True, return_counts=True)
-            if aggregator == "count":
-                return uk, cnt
-            if aggregator == "sum":
-                out = torch.zeros(uk.numel(), dtype=torch.int64,
-                                  device=k.device)
-                out.index_add_(0, inverse, v)
-                return uk, out
-            if aggregator == "sum_f64":
-                out = torch.zeros(uk.numel(), dtype=torch.float64,
-                                  device=k.device)
-                out.index_add_(0, inverse, v.view(torch.float64))
-                return uk, out
-            red = "amin" if aggregator == "min" else "amax"
-            out = torch.empty(uk.numel(), dtype=torch.int64, device=k.device)
-            out.scatter_reduce_(0, inverse, v, reduce=red,
-                                include_self=False)
-            return uk, out
+                return pairs[0::2], pairs[1::2]
+            from .ops.radix import reduce_by_key_aos
+            return reduce_by_key_aos(pairs, aggregator)
         # ---- CPU path: numpy mirror of the device semantics ----
         import numpy as np
         k, v = self._drain_aos_pairs()

@@ -31,7 +31,12 @@ class ReduceByKeyResult:
 class ReduceByKey:
     def __init__(self, engine: Engine, rows_per_executor: int,
                  num_keys: int = 1 << 20, partitions_per_executor: int = 32,
-                 device: str = "cpu", validate: bool = False, seed: int = 0):
+                 device: str = "cpu", validate: bool = False, seed: int = 0,
+                 aggregator: str = "sum", map_side_combine: bool = False):
+        from ..aggregate import check_aggregator
+        check_aggregator(aggregator)
+        self.aggregator = aggregator
+        self.map_side_combine = map_side_combine
         self.engine = engine
         self.n = rows_per_executor
         self.device = device
@@ -66,13 +71,18 @@ class ReduceByKey:
             w.write_device_batch(self.keys, self.vals)
         else:
             w.write_batch(self.keys, self.vals)
-        w.stop(True, partitioner=self.part)
+        # map-side combine ships one row per distinct key of this map task
+        # (Spark's reduceByKey default); the reader then merges
+        w.stop(True, partitioner=self.part,
+               combiner=self.aggregator if self.map_side_combine else None)
         eng.barrier()
         lo, hi = eng.rank * self.ppe, (eng.rank + 1) * self.ppe - 1
         reader = eng.manager.get_reader(handle, lo, hi)
         # the reader's GENERIC aggregate hookup (RdmaShuffleReader.scala:
-        # 61-114 role): sort by key + segmented sum, device-side on GPU
-        uk, sums = reader.read_aos(aggregator="sum")
+        # 61-114 role): sort by key + segmented reduction, device-side on
+        # GPU (ops/csrc/reduce.hip)
+        uk, sums = reader.read_aos(aggregator=self.aggregator,
+                                   map_side_combined=self.map_side_combine)
         if self.device == "cuda":
             import torch
             torch.cuda.synchronize()
@@ -88,9 +98,15 @@ class ReduceByKey:
 
     def _validate(self, uk, sums) -> None:
         """Single-rank oracle: this rank's groups must equal the dict-based
-        sums of every rank's rows hashing to this rank's partitions."""
+        reduction of every rank's rows hashing to this rank's partitions.
+        Integer aggregators match exactly (payloads are below 2^20, so the
+        signed and unsigned readings of min/max agree); sum_f64 reads the
+        payload bits as doubles and is compared to math.fsum within the
+        any-order summation bound."""
+        import math
         eng = self.engine
-        want: dict = {}
+        agg = self.aggregator
+        rows: dict = {}
         for r in range(eng.world_size):
             # regenerate rank r's rows deterministically
             rng = np.random.default_rng(self.seed * 101 + r)
@@ -99,10 +115,25 @@ class ReduceByKey:
             pids = self.part.partition_ids(k)
             mine = (pids >= eng.rank * self.ppe) & \
                    (pids < (eng.rank + 1) * self.ppe)
-            for kk, vv in zip(k[mine], v[mine]):
-                want[int(kk)] = want.get(int(kk), 0) + int(vv)
+            if agg == "sum_f64":
+                v = v.view(np.float64)
+            for kk, vv in zip(k[mine].tolist(), v[mine].tolist()):
+                rows.setdefault(kk, []).append(vv)
         if self.device == "cuda":
             uk = uk.cpu().numpy().view(np.uint64)
-            sums = sums.cpu().numpy().view(np.uint64)
-        got = dict(zip(uk.tolist(), sums.tolist()))
+            sums = sums.cpu().numpy()
+        uk = np.asarray(uk)
+        sums = np.asarray(sums)
+        if agg == "sum_f64":
+            got = dict(zip(uk.tolist(), sums.view(np.float64).tolist()))
+            assert got.keys() == rows.keys(), (len(got), len(rows))
+            for kk, vs in rows.items():
+                bound = 2 * (len(vs) - 1) * 2.0 ** -53 * math.fsum(
+                    abs(x) for x in vs)
+                assert abs(got[kk] - math.fsum(vs)) <= bound, kk
+            return
+        fold = {"sum": lambda vs: sum(vs) & (2 ** 64 - 1), "count": len,
+                "min": min, "max": max}[agg]
+        want = {kk: fold(vs) for kk, vs in rows.items()}
+        got = dict(zip(uk.tolist(), sums.view(np.uint64).tolist()))
         assert got == want, (len(got), len(want))

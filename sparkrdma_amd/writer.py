@@ -149,9 +149,34 @@ class ShuffleWriter:
 
     # -- commit ---------------------------------------------------------
 
-    def stop(self, success: bool, partitioner=None) -> None:
+    def stop(self, success: bool, partitioner=None, combiner=None,
+             combine_key_bits: int = 64) -> None:
+        """Partition, lay out and publish this map task's output.
+
+        ``combiner`` (one of ShuffleReader.AGGREGATORS) turns on the
+        map-side combine of (u64 key, u64 value) rows — what Spark's
+        sort-shuffle writer does for the reference when
+        ``dep.mapSideCombine`` is set: the task's rows are sorted by key,
+        collapsed to ONE row per distinct key, and only those are
+        partitioned and shipped. After "count" the shipped value is this
+        map's row count for the key. The reduce side must then merge:
+        ``read_aos(aggregator=combiner, map_side_combined=True)``.
+        ``metrics.records_written`` / ``bytes_written`` count the combined
+        rows; ``metrics.extra["records_combined_in"]`` the input rows.
+
+        ``combine_key_bits`` < 64 sorts by the low key bits only, which
+        saves radix passes for callers with a bounded key space. Keys that
+        differ above those bits then fragment each other's runs and the
+        combine is partial: more rows are shipped, but the result is still
+        correct because the reduce side merges.
+
+        Supported on the 16-byte lanes (write_device_batch, and write_batch
+        with 8-byte values); ``combiner=None`` is the plain path.
+        """
         if self._stopped:
             return
+        if combiner is not None:
+            self._check_combiner(combiner, combine_key_bits)
         self._stopped = True
         if not success:
             return
@@ -159,19 +184,46 @@ class ShuffleWriter:
         if getattr(self, "_gpu_records", None):
             self._commit_gpu_records(partitioner)
         elif getattr(self, "_gpu_batches", None):
-            self._commit_gpu(partitioner)
+            self._commit_gpu(partitioner, combiner, combine_key_bits)
         else:
             if self._byte_records is not None:
                 segments = [b"".join(recs) for recs in self._byte_records]
             else:
-                segments = self._partition_fixed(partitioner)
+                segments = self._partition_fixed(partitioner, combiner,
+                                                 combine_key_bits)
             self._commit_segments(segments)
         self.metrics.write_ns += time.perf_counter_ns() - t0
         lm = getattr(self.manager, "lifetime_metrics", None)
         if lm is not None:
             lm.merge(self.metrics)
 
-    def _partition_fixed(self, partitioner) -> List[bytes]:
+    def _check_combiner(self, combiner, combine_key_bits) -> None:
+        """Reject what map-side combine does not cover, before any state
+        changes (stop() can then be called again without a combiner)."""
+        from .aggregate import check_aggregator
+        check_aggregator(combiner, "combiner")
+        if not 1 <= combine_key_bits <= 64:
+            raise ValueError("combine_key_bits must be in [1, 64]")
+        if getattr(self, "_gpu_records", None):
+            raise ValueError("map-side combine does not cover wide records "
+                             "(write_device_records)")
+        if self._byte_records is not None:
+            raise ValueError("map-side combine does not cover the pickled "
+                             "lane (write_records)")
+        for _k, v in getattr(self, "_gpu_batches", None) or []:
+            if v is None:
+                raise ValueError("map-side combine needs values; a "
+                                 "value-less batch was written")
+        for v in self._value_batches:
+            if v is None:
+                raise ValueError("map-side combine needs values; a "
+                                 "value-less batch was written")
+            if v.ndim != 2 or v.shape[1] != 8:
+                raise ValueError("map-side combine needs 8-byte values, got "
+                                 f"shape {v.shape}")
+
+    def _partition_fixed(self, partitioner, combiner=None,
+                         combine_key_bits: int = 64) -> List[bytes]:
         R = self.handle.num_partitions
         if not self._key_batches:
             return [b""] * R
@@ -181,6 +233,21 @@ class ShuffleWriter:
         if self._value_batches and self._value_batches[0] is not None:
             vals = (self._value_batches[0] if len(self._value_batches) == 1
                     else np.concatenate(self._value_batches))
+        if combiner is not None:
+            # numpy mirror of the GPU lane: stable sort by the low key
+            # bits, then one row per run of equal (full) keys
+            from .aggregate import reduce_sorted_np
+            self.metrics.extra["records_combined_in"] = \
+                self.metrics.extra.get("records_combined_in", 0) + len(keys)
+            v64 = np.ascontiguousarray(vals).view(np.uint64).reshape(-1)
+            skey = keys if combine_key_bits >= 64 else \
+                keys & np.uint64((1 << combine_key_bits) - 1)
+            order = np.argsort(skey, kind="stable")
+            keys, red = reduce_sorted_np(keys[order], v64[order], combiner)
+            if red.dtype == np.float64:
+                red = red.view(np.uint64)
+            vals = np.ascontiguousarray(red.astype(np.uint64, copy=False)) \
+                .view(np.uint8).reshape(-1, 8)
         pids = partitioner.partition_ids(keys)
         order = np.argsort(pids, kind="stable")
         keys_sorted = keys[order]
@@ -218,7 +285,8 @@ class ShuffleWriter:
         func, shift, nparts = params
         return func, shift, nparts, min(max(nbits, 4), 12)
 
-    def _commit_gpu(self, partitioner) -> None:
+    def _commit_gpu(self, partitioner, combiner=None,
+                    combine_key_bits: int = 64) -> None:
         """Map-side GPU write: one radix pass whose scatter writes each
         partition's [keys|vals] segment STRAIGHT into its final position in
         HBM pool blocks (the north-star replacement for the reference's
@@ -235,6 +303,23 @@ class ShuffleWriter:
                 else torch.cat([b[0] for b in batches]))
         vals = (batches[0][1] if len(batches) == 1 or batches[0][1] is None
                 else torch.cat([b[1] for b in batches]))
+        if combiner is not None:
+            # map-side combine: sort this task's rows by key, collapse
+            # each run to one row (ops/csrc/reduce.hip), carry on with
+            # the combined rows
+            from .ops.radix import reduce_by_key_aos, sort_pairs_aos
+            self.metrics.extra["records_combined_in"] = \
+                self.metrics.extra.get("records_combined_in", 0) \
+                + keys.numel()
+            pr = torch.empty(2 * keys.numel(), dtype=torch.int64,
+                             device=keys.device)
+            pr[0::2] = keys
+            pr[1::2] = vals
+            # whole 8-bit digits: extra sorted bits only combine more
+            pr = sort_pairs_aos(pr, 0, min(-(-combine_key_bits // 8) * 8, 64))
+            keys, vals = reduce_by_key_aos(pr, combiner)
+            if vals.dtype != torch.int64:
+                vals = vals.view(torch.int64)
         if (R - 1).bit_length() > 12:
             # > 4096 partitions: route through the wide-record two-level
             # pid radix (records = the interleaved 16-B AoS pairs, or the
