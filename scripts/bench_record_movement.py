@@ -7,6 +7,9 @@ Times, for 100-byte and 256-byte records:
   * sort_records(fuse=True)   (pair extract + radix passes + fused gather)
   * sort_records with the tie repair on and off, on random keys and on
     all-equal keys (the input that forces the fallback to the full passes)
+  * the reduce-side fetch of the records: read_batch (hipMemcpyAsync) +
+    extract_pairs against read_records_batch (the fused copy + pair-extract
+    kernel), source and destination at 4-byte-only alignment
 with device events, median of --launches launches, at a size far past the
 256 MB Infinity Cache. GB/s counts each record's bytes ONCE (n * W / time):
 the kernels read and write every record once, so memory traffic is at
@@ -122,11 +125,52 @@ def bench_width(hs, W, total_bytes, launches):
     sort_case("sort equal keys", 0)
 
 
+def bench_fetch(hs, W, total_bytes, launches):
+    """Fetch n W-byte records into an arena and produce their pairs: plain
+    copy + extract_pairs against the fused kernel. src sits 4 and dst 12
+    bytes into their buffers (mutually 8 mod 16). TB/s counts each byte
+    once: records read + records written + pairs written."""
+    n = total_bytes // W
+    dev = "cuda"
+    g = torch.Generator(device=dev)
+    g.manual_seed(W + 1)
+    src_buf = torch.randint(-2**63, 2**63 - 1, (n * W // 8 + 4,),
+                            dtype=torch.int64, device=dev,
+                            generator=g).view(torch.uint8)
+    dst_buf = torch.empty(n * W + 32, dtype=torch.uint8, device=dev)
+    pairs = torch.empty(2 * n, dtype=torch.int64, device=dev)
+    src, dst = src_buf.data_ptr() + 4, dst_buf.data_ptr() + 12
+    s = torch.cuda.current_stream().cuda_stream
+    moved = 2 * n * W + 16 * n
+
+    # the copy engine runs on its own streams: fence them with the events
+    # of the current stream by waiting for the engine's completion event
+    def plain():
+        hs.wait_event(hs.read_batch(0, [dst], [src], [n * W]))
+        hs.extract_pairs(dst, n, W, 10, pairs.data_ptr(), s)
+
+    def copy_only():
+        hs.wait_event(hs.read_batch(0, [dst], [src], [n * W]))
+
+    def fused():
+        hs.wait_event(hs.read_records_batch(
+            0, [dst], [src], [n * W], W, 10, [pairs.data_ptr()], [0]))
+
+    for name, fn, nbytes in (("read_batch alone", copy_only, 2 * n * W),
+                             ("read_batch + extract_pairs", plain, moved),
+                             ("read_records_batch (fused)", fused, moved)):
+        ms = timed_ms(fn, launches)
+        print(f"W={W:4d} n={n:10d} fetch: {name:28s} {ms:9.3f} ms  "
+              f"{nbytes / ms / 1e9:6.2f} TB/s of bytes moved", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gb", type=float, default=4.0,
                     help="record bytes per case (default 4 GB)")
     ap.add_argument("--launches", type=int, default=11)
+    ap.add_argument("--only-fetch", action="store_true",
+                    help="run only the reduce-side fetch cases")
     args = ap.parse_args()
     if args.launches < 10:
         ap.error("--launches must be at least 10")
@@ -134,7 +178,10 @@ def main():
         sys.exit("bench_record_movement needs a GPU")
     hs = load()
     for W in (100, 256):
-        bench_width(hs, W, int(args.gb * 1e9), args.launches)
+        if not args.only_fetch:
+            bench_width(hs, W, int(args.gb * 1e9), args.launches)
+            torch.cuda.empty_cache()
+        bench_fetch(hs, W, int(args.gb * 1e9), args.launches)
         torch.cuda.empty_cache()
 
 

@@ -99,6 +99,13 @@ class ShuffleConf:
     # intra-node xGMI/shm paths never compress
     tcp_compress: bool = False        # zlib-1 per chunk
     tcp_chunk_size: int = 4 << 20     # streaming chunk (pinned D2H unit)
+    # wide-record readers that pass a record spec: which one-sided fetches
+    # run as the fused copy + pair-extract kernel instead of a plain copy
+    #   local: sources owned by this executor (default)
+    #   host:  also peer executors' slabs on this host (a compute-kernel
+    #          copy over xGMI instead of hipMemcpyAsync)
+    #   off:   none — every fetch is a plain copy, pairs extracted after
+    fused_record_fetch: str = "local"
 
     def __post_init__(self) -> None:
         self._validate_range("recv_queue_depth", self.recv_queue_depth, 16, 1 << 20)
@@ -113,6 +120,10 @@ class ShuffleConf:
         if self.transport not in ("auto", "shm", "ipc", "rccl", "tcp"):
             raise ConfError(
                 f"transport must be auto|shm|ipc|rccl|tcp, got {self.transport!r}")
+        if self.fused_record_fetch not in ("local", "host", "off"):
+            raise ConfError(
+                "fusedRecordFetch must be local|host|off, got "
+                f"{self.fused_record_fetch!r}")
 
     @staticmethod
     def _validate_range(name: str, value: int, lo: int, hi: int) -> None:
@@ -155,6 +166,7 @@ class ShuffleConf:
         "executorCores": ("executor_cores", int),
         "tcpCompress": ("tcp_compress", None),
         "tcpChunkSize": ("tcp_chunk_size", parse_bytes),
+        "fusedRecordFetch": ("fused_record_fetch", str),
     }
 
     @classmethod

@@ -295,6 +295,21 @@ class GpuDataPlane:
         peer = self._stream_slot(exec_id)
         return self.hs.read_batch(peer, [dst_ptr], [base + addr], [length])
 
+    def issue_read_records_into(self, key: int, addr: int, length: int,
+                                dst_ptr: int, rec_bytes: int, key_bytes: int,
+                                pairs_ptr: int, idx_base: int) -> int:
+        """``issue_read_into`` for a run of whole ``rec_bytes``-byte
+        records: the fused kernel copies the run and writes each record's
+        (prefix, aux) pair — aux index ``idx_base + i`` — to ``pairs_ptr``
+        (kernels.hip fetch_records). Same streams, same completion event."""
+        exec_id, _ = split_key(key)
+        self.hs.set_device(self.device)
+        base = self.resolve(key)
+        peer = self._stream_slot(exec_id)
+        return self.hs.read_records_batch(
+            peer, [dst_ptr], [base + addr], [length], rec_bytes, key_bytes,
+            [pairs_ptr], [idx_base])
+
     def _stream_slot(self, exec_id: int) -> int:
         """Copy-stream selector: the peer's GPU ordinal — streams map to
         xGMI links, not executor ids."""

@@ -308,10 +308,12 @@ class ShuffleManager:
         return ShuffleWriter(self, handle, map_id)
 
     def get_reader(self, handle: ShuffleHandle, start_partition: int,
-                   end_partition: int, arena=None):
+                   end_partition: int, arena=None, records=None):
+        """``records``: optional wide-record spec ``(rec_bytes, key_bytes,
+        pairs_tensor)`` — see FetcherIterator."""
         from .reader import ShuffleReader
         return ShuffleReader(self, handle, start_partition, end_partition,
-                             arena=arena)
+                             arena=arena, records=records)
 
     def unregister_shuffle(self, shuffle_id: int, notify_driver: bool = True) -> None:
         # release served blocks (liveness discipline: blocks stay alive until

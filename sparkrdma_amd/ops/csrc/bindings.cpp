@@ -35,6 +35,11 @@ PYBIND11_MODULE(_hipshuffle, m) {
   m.def("read_batch", &hs::read_batch_ids, py::arg("peer"), py::arg("dsts"),
         py::arg("srcs"), py::arg("sizes"),
         py::call_guard<py::gil_scoped_release>());
+  m.def("read_records_batch", &hs::read_records_batch_ids, py::arg("peer"),
+        py::arg("dsts"), py::arg("srcs"), py::arg("sizes"),
+        py::arg("rec_bytes"), py::arg("key_bytes"), py::arg("pairs_ptrs"),
+        py::arg("idx_bases"), py::call_guard<py::gil_scoped_release>());
+  m.def("fetch_block_records", &hs::fetch_block_records);
   m.def("poll_event", &hs::poll_event,
         py::call_guard<py::gil_scoped_release>());
   m.def("wait_event", &hs::wait_event,

@@ -19,6 +19,15 @@ void enable_peer_access(int peer_device);
 uint64_t read_batch_ids(int peer, const std::vector<uintptr_t>& dsts,
                         const std::vector<uintptr_t>& srcs,
                         const std::vector<size_t>& sizes);
+// like read_batch_ids, but every (dst, src, size) is a run of whole
+// rec_bytes-byte records moved by fetch_records, which also writes the
+// run's (prefix, aux) pairs to pairs_ptrs[i] with indices from idx_bases[i]
+uint64_t read_records_batch_ids(int peer, const std::vector<uintptr_t>& dsts,
+                                const std::vector<uintptr_t>& srcs,
+                                const std::vector<size_t>& sizes,
+                                uint32_t rec_bytes, uint32_t key_bytes,
+                                const std::vector<uintptr_t>& pairs_ptrs,
+                                const std::vector<uint64_t>& idx_bases);
 bool poll_event(uint64_t id);
 void wait_event(uint64_t id);
 int64_t tcp_recv_chunks(int fd, uintptr_t out, uint64_t total);
@@ -50,6 +59,10 @@ void gather_records(uintptr_t recs, uintptr_t pairs, uint64_t n,
                     uintptr_t dst_addr, uintptr_t dstart, int shift,
                     uint32_t mask, int func, uint32_t nparts,
                     uintptr_t stream);
+uint32_t fetch_block_records(uint32_t rec_bytes);
+void fetch_records(uintptr_t dst, uintptr_t src, uint64_t n,
+                   uint32_t rec_bytes, uint32_t key_bytes, uintptr_t pairs,
+                   uint64_t idx_base, uintptr_t stream);
 size_t sort_workspace_bytes(uint32_t n);
 int sort_pairs_u64(uintptr_t keys, uintptr_t vals, uintptr_t tmp_keys,
                    uintptr_t tmp_vals, uint32_t n, int start_bit, int end_bit,

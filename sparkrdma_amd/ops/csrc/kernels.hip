@@ -966,6 +966,12 @@ __global__ void onesweep_digit_bases_kernel(
 //     W-byte contiguous chunks; both sides move each record exactly once.
 // Traffic: ~2.2x the record bytes + ~64 B/pass for the 16 B pairs —
 // pair passes cost 16% of what full-record passes would at W = 100.
+// extract_pairs itself re-reads practically every 128-byte line of its
+// input at W = 100 (10 key bytes per 100-byte record), i.e. one more
+// pass over the records. The map side needs that pass (the gather cannot
+// place a record before its pair exists); the reduce side does not: its
+// one-sided fetch moves every record through registers anyway, and
+// fetch_records_kernel emits the pairs from there.
 
 // Key layout inside a record: bytes [0,8) u64 LE prefix, bytes [8,10)
 // u16 LE low bits (key_bytes == 8 or 10); 80-bit order = (prefix, lo).
@@ -1093,6 +1099,147 @@ void gather_records(uintptr_t recs, uintptr_t pairs, uint64_t n,
                      reinterpret_cast<const uint64_t*>(dst_addr),
                      reinterpret_cast<const uint32_t*>(dstart), shift, mask,
                      func, nparts);
+  HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------
+// Fused one-sided fetch of wide records: copy a run of n whole W-byte
+// records src -> dst AND emit every record's (prefix, aux) pair, exactly
+// what extract_pairs_kernel writes for pid_func < 0. The reduce side used
+// to copy the run (hipMemcpyAsync) and then read practically every line of
+// the arena again to pick 10 key bytes out of each 100-byte record; here
+// the key words are taken from the registers that move them.
+//
+// A block owns a tile of whole records, which is one contiguous word range
+// on both sides, and moves it one dword per lane (src and dst are only
+// 4-byte aligned, independently of each other), U independent loads per
+// lane before the first store as in copy_record_words. Word q of the tile
+// is word q % w4 of record q / w4, tracked with the same block-uniform
+// (BS / w4, BS % w4) stepping; a lane holding word 0, 1 or 2 of a record
+// also drops it into the LDS key table. After one barrier, one thread per
+// record assembles the pair and the block stores the pairs as coalesced
+// 16-byte stores.
+//
+// INVARIANT: every word of [src, src + n * w4) is loaded exactly once and
+// nothing outside it is touched — lanes past the end of the last tile load
+// nothing — so the kernel is equally valid for a peer-mapped source. dst
+// gets exactly [dst, dst + n * w4), pairs exactly [pairs, pairs + 2n).
+//
+// Tile: about 4096 words (16 KB, two batches) per block. With src and dst
+// 4 and 12 bytes off a 16-byte boundary, 4 GB of 100-byte records moved at
+// 4.5-4.7 TB/s (records read + written + pairs written) with 1024-record
+// tiles and at 5.25-5.55 TB/s with 128..256-record tiles, against 5.6 TB/s
+// for either with both sides 16-byte aligned; 16 bytes per lane at 4-byte
+// alignment (the tile is one contiguous range, so there is no per-record
+// tail) was no faster than one dword per lane at these tile sizes
+// (profiles/r06_fused_fetch.md).
+constexpr uint32_t FETCH_MAX_RECS = 1024;  // per block: 12 KB key table
+constexpr uint32_t FETCH_BLOCK_WORDS = 4096;
+constexpr int FETCH_BATCH = GATHER_BATCH;
+
+static inline uint32_t fetch_block_records_w4(uint32_t w4) {
+  uint32_t rpb = FETCH_BLOCK_WORDS / w4;
+  if (rpb > FETCH_MAX_RECS) rpb = FETCH_MAX_RECS;
+  return rpb < 1 ? 1 : rpb;
+}
+
+// One batch of the tile: U words per lane, loads first. WHOLE (every lane
+// has all U words) is decided per batch for the whole block and compiled
+// as its own body, so neither the loads nor the stores of a whole batch
+// sit behind a per-lane test or a wait that only the tile's last batch
+// needs. (r, o) = record and word-in-record of the lane's next word.
+template <int BS, int U, bool WHOLE>
+__device__ __forceinline__ void fetch_batch(
+    const uint32_t* __restrict__ s, uint32_t* __restrict__ d,
+    uint32_t* keytab, uint32_t q0, uint32_t total, uint32_t w4, uint32_t dr,
+    uint32_t dc, uint32_t& r, uint32_t& o) {
+  uint32_t v[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const uint32_t q = q0 + (uint32_t)u * BS + threadIdx.x;
+    v[u] = (WHOLE || q < total) ? s[q] : 0u;
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const uint32_t q = q0 + (uint32_t)u * BS + threadIdx.x;
+    if (WHOLE || q < total) {
+      d[q] = v[u];
+      if (o < 3) keytab[r * 3 + o] = v[u];
+    }
+    o += dc;
+    r += dr;
+    if (o >= w4) {
+      o -= w4;
+      ++r;
+    }
+  }
+}
+
+template <int BS, int U>
+__global__ __launch_bounds__(BS) void fetch_records_kernel(
+    const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, uint64_t n,
+    uint32_t w4 /* rec_bytes/4 */,
+    uint32_t recs_per_block /* <= FETCH_MAX_RECS */, uint32_t key_bytes,
+    uint64_t* __restrict__ pairs, uint64_t idx_base) {
+  __shared__ uint32_t keytab[FETCH_MAX_RECS * 3];  // words 0..2 per record
+  const uint64_t r0 = (uint64_t)blockIdx.x * recs_per_block;
+  if (r0 >= n) return;
+  const uint32_t nr = (uint32_t)min((uint64_t)recs_per_block, n - r0);
+  const uint32_t total = nr * w4;
+  const uint32_t* __restrict__ s = src + r0 * w4;
+  uint32_t* __restrict__ d = dst + r0 * w4;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t dr = BS / w4, dc = BS % w4;
+  uint32_t r = tid / w4, o = tid % w4;
+  const uint32_t whole_end = total - total % (BS * U);
+  uint32_t q0 = 0;
+#pragma unroll 1
+  for (; q0 < whole_end; q0 += BS * U)
+    fetch_batch<BS, U, true>(s, d, keytab, q0, total, w4, dr, dc, r, o);
+  if (q0 < total)
+    fetch_batch<BS, U, false>(s, d, keytab, q0, total, w4, dr, dc, r, o);
+  __syncthreads();
+  for (uint32_t j = tid; j < nr; j += BS) {
+    const uint64_t prefix =
+        ((uint64_t)keytab[j * 3 + 1] << 32) | keytab[j * 3];
+    uint64_t aux = idx_base + r0 + j;
+    // word 2 exists whenever key_bytes > 8 (rec_bytes >= 12 host-side)
+    if (key_bytes > 8) aux |= (uint64_t)(uint16_t)keytab[j * 3 + 2] << 48;
+    reinterpret_cast<ulonglong2*>(pairs)[r0 + j] = ulonglong2{prefix, aux};
+  }
+}
+
+uint32_t fetch_block_records(uint32_t rec_bytes) {
+  if (rec_bytes % 4 || rec_bytes < 8)
+    throw std::runtime_error("rec_bytes must be a multiple of 4, >= 8");
+  return fetch_block_records_w4(rec_bytes / 4);
+}
+
+void fetch_records(uintptr_t dst, uintptr_t src, uint64_t n,
+                   uint32_t rec_bytes, uint32_t key_bytes, uintptr_t pairs,
+                   uint64_t idx_base, uintptr_t stream) {
+  if (rec_bytes % 4 || rec_bytes < 8)
+    throw std::runtime_error("rec_bytes must be a multiple of 4, >= 8");
+  if (key_bytes != 8 && key_bytes != 10)
+    throw std::runtime_error("key_bytes must be 8 or 10");
+  if (key_bytes > 8 && rec_bytes < 12)
+    throw std::runtime_error("key_bytes 10 needs rec_bytes >= 12");
+  if ((n >> 48) || ((idx_base + n) >> 48))
+    throw std::runtime_error("idx_base + n exceeds 2^48");
+  if ((src | dst) % 4 || pairs % 16)
+    throw std::runtime_error(
+        "fetch_records: src/dst need 4-byte, pairs 16-byte alignment");
+  if (n == 0) return;
+  const uint32_t w4 = rec_bytes / 4;
+  const uint32_t rpb = fetch_block_records_w4(w4);
+  const uint64_t grid = (n + rpb - 1) / rpb;
+  if (grid > 0x7FFFFFFF) throw std::runtime_error("grid too large");
+  hipLaunchKernelGGL((fetch_records_kernel<BLOCK, FETCH_BATCH>),
+                     dim3((uint32_t)grid), dim3(BLOCK), 0,
+                     reinterpret_cast<hipStream_t>(stream),
+                     reinterpret_cast<const uint32_t*>(src),
+                     reinterpret_cast<uint32_t*>(dst), n, w4, rpb, key_bytes,
+                     reinterpret_cast<uint64_t*>(pairs), idx_base);
   HIP_CHECK(hipGetLastError());
 }
 

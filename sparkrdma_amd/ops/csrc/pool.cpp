@@ -13,6 +13,7 @@
 // (block_pool.py); this layer only provides slabs and copies.
 
 #include "common.h"
+#include "hipshuffle.h"
 
 #include <sys/socket.h>
 
@@ -157,12 +158,35 @@ class CopyEngine {
                                reinterpret_cast<void*>(srcs[i]), sizes[i],
                                hipMemcpyDefault, s));
     }
-    hipEvent_t ev = acquire_event();
-    HIP_CHECK(hipEventRecord(ev, s));
-    uint64_t id = next_event_.fetch_add(1);
-    std::lock_guard<std::mutex> g(ev_mu_);
-    events_[id] = ev;
-    return id;
+    return signal(s);
+  }
+
+  // read_batch for runs of whole records: the fused copy + pair-extract
+  // kernel (kernels.hip fetch_records) takes the place of hipMemcpyAsync,
+  // on the same rotating per-peer streams and behind the same single
+  // completion event.
+  uint64_t read_records_batch(int peer, const std::vector<uintptr_t>& dsts,
+                              const std::vector<uintptr_t>& srcs,
+                              const std::vector<size_t>& sizes,
+                              uint32_t rec_bytes, uint32_t key_bytes,
+                              const std::vector<uintptr_t>& pairs_ptrs,
+                              const std::vector<uint64_t>& idx_bases) {
+    const size_t m = dsts.size();
+    if (srcs.size() != m || sizes.size() != m || pairs_ptrs.size() != m ||
+        idx_bases.size() != m)
+      throw std::runtime_error("read_records_batch: list lengths differ");
+    if (rec_bytes == 0)
+      throw std::runtime_error("read_records_batch: rec_bytes is 0");
+    for (size_t i = 0; i < m; ++i)
+      if (sizes[i] % rec_bytes)
+        throw std::runtime_error(
+            "read_records_batch: size is not a whole number of records");
+    hipStream_t s = stream_for(peer);
+    for (size_t i = 0; i < m; ++i)
+      fetch_records(dsts[i], srcs[i], sizes[i] / rec_bytes, rec_bytes,
+                    key_bytes, pairs_ptrs[i], idx_bases[i],
+                    reinterpret_cast<uintptr_t>(s));
+    return signal(s);
   }
 
   // true = complete (event recycled), false = still in flight
@@ -194,6 +218,16 @@ class CopyEngine {
   }
 
  private:
+  // the "signaled last WR": one recycled event behind what was enqueued
+  uint64_t signal(hipStream_t s) {
+    hipEvent_t ev = acquire_event();
+    HIP_CHECK(hipEventRecord(ev, s));
+    uint64_t id = next_event_.fetch_add(1);
+    std::lock_guard<std::mutex> g(ev_mu_);
+    events_[id] = ev;
+    return id;
+  }
+
   hipEvent_t acquire_event() {
     {
       std::lock_guard<std::mutex> g(ev_mu_);
@@ -238,6 +272,15 @@ uint64_t read_batch_ids(int peer, const std::vector<uintptr_t>& dsts,
                         const std::vector<uintptr_t>& srcs,
                         const std::vector<size_t>& sizes) {
   return copy_engine().read_batch(peer, dsts, srcs, sizes);
+}
+uint64_t read_records_batch_ids(int peer, const std::vector<uintptr_t>& dsts,
+                                const std::vector<uintptr_t>& srcs,
+                                const std::vector<size_t>& sizes,
+                                uint32_t rec_bytes, uint32_t key_bytes,
+                                const std::vector<uintptr_t>& pairs_ptrs,
+                                const std::vector<uint64_t>& idx_bases) {
+  return copy_engine().read_records_batch(peer, dsts, srcs, sizes, rec_bytes,
+                                          key_bytes, pairs_ptrs, idx_bases);
 }
 bool poll_event(uint64_t id) { return copy_engine().poll(id); }
 void wait_event(uint64_t id) { return copy_engine().wait(id); }

@@ -30,6 +30,7 @@ pool (they are genuinely blocking OS calls).
 
 from __future__ import annotations
 
+import bisect
 import os
 import queue
 import random
@@ -132,7 +133,16 @@ class FetcherIterator:
     def __init__(self, manager: ShuffleManager, handle: ShuffleHandle,
                  start_partition: int, end_partition: int,
                  num_workers: int = 8, seed: Optional[int] = None,
-                 arena: Optional[object] = None):
+                 arena: Optional[object] = None,
+                 records: Optional[tuple] = None):
+        """``records``: optional wide-record spec ``(rec_bytes, key_bytes,
+        pairs)``, ``pairs`` an int64 device tensor with two elements per
+        record the arena hint can hold. Event-lane fetches whose arena
+        offset and length are whole records then run as the fused copy +
+        pair-extract kernel: record ``arena_off // rec_bytes + i`` gets its
+        (prefix, aux) pair at that index of ``pairs``. ``pair_ranges()``
+        and ``pairs_written()`` say which arena ranges were served that
+        way; every other fetch is a plain copy and the caller extracts."""
         self.manager = manager
         self.handle = handle
         self.start_partition = start_partition
@@ -169,6 +179,14 @@ class FetcherIterator:
         self._blocking_arena_inflight = 0  # pool fetches writing the arena
         self._paused = False               # arena-growth issue gate
         self._completion_thread: Optional[threading.Thread] = None
+        # fused record lane (conf.fused_record_fetch); off once the arena
+        # is allocated late or grows — callers re-extract such arenas whole
+        self._records = records
+        self._fuse_mode = (getattr(conf, "fused_record_fetch", "local")
+                           if records is not None and arena is not None
+                           else "off")
+        self._pair_starts: List[int] = []  # sorted arena offsets ...
+        self._pair_ends: dict = {}         # ... -> end of the fused range
         self._pool.submit(self._start_async)
 
     # ------------------------------------------------------------------
@@ -273,6 +291,7 @@ class FetcherIterator:
             deferred, self._deferred = self._deferred, []
         if deferred:
             import torch
+            self._fuse_mode = "off"
             total = sum(f.length for f in deferred)
             dev = f"cuda:{self.manager.gpu.device}"
             if self._arena_buf is None and self._arena_used == 0:
@@ -358,9 +377,18 @@ class FetcherIterator:
             # event-driven lane: enqueue the xGMI copy; the completion
             # thread polls the event (no blocked thread per fetch)
             try:
-                ev = mgr.gpu.issue_read_into(
-                    f.key, f.addr, f.length,
-                    self._arena_buf.data_ptr() + f.arena_off)
+                dst = self._arena_buf.data_ptr() + f.arena_off
+                if self._fused(f, owner):
+                    W, key_bytes, pairs = self._records
+                    idx_base = f.arena_off // W
+                    ev = mgr.gpu.issue_read_records_into(
+                        f.key, f.addr, f.length, dst, W, key_bytes,
+                        pairs.data_ptr() + 16 * idx_base, idx_base)
+                    with self._lock:
+                        bisect.insort(self._pair_starts, f.arena_off)
+                        self._pair_ends[f.arena_off] = f.arena_off + f.length
+                else:
+                    ev = mgr.gpu.issue_read_into(f.key, f.addr, f.length, dst)
             except BaseException as e:
                 self._results.put(FetchResult(f, None, error=e))
                 return
@@ -372,6 +400,32 @@ class FetcherIterator:
                 with self._lock:
                     self._blocking_arena_inflight += 1
             self._pool.submit(self._do_fetch_blocking, f)
+
+    def _fused(self, f: CoalescedFetch, owner: int) -> bool:
+        """Does this event-lane fetch take the fused record kernel?"""
+        mode = self._fuse_mode
+        if mode == "off" or (mode == "local"
+                             and owner != self.manager.executor_id):
+            return False
+        W, _key_bytes, pairs = self._records
+        return (f.arena_off % W == 0 and f.length % W == 0
+                and f.addr % 4 == 0
+                and self._arena_buf.data_ptr() % 4 == 0
+                and pairs.data_ptr() % 16 == 0
+                and 2 * ((f.arena_off + f.length) // W) <= pairs.numel())
+
+    def pair_ranges(self) -> List[tuple]:
+        """Arena ranges ``(offset, length)`` whose pairs the fused lane
+        wrote (complete once the iterator is drained), by offset."""
+        with self._lock:
+            return [(a, self._pair_ends[a] - a) for a in self._pair_starts]
+
+    def pairs_written(self, off: int, length: int) -> bool:
+        """True if arena bytes [off, off + length) lie in one fused fetch."""
+        with self._lock:
+            i = bisect.bisect_right(self._pair_starts, off) - 1
+            return (i >= 0 and off + length
+                    <= self._pair_ends[self._pair_starts[i]])
 
     def _ensure_completion_thread(self) -> None:
         if self._completion_thread is None:
@@ -527,14 +581,15 @@ class ShuffleReader:
     from .aggregate import AGGREGATORS
 
     def __init__(self, manager: ShuffleManager, handle: ShuffleHandle,
-                 start_partition: int, end_partition: int, arena=None):
+                 start_partition: int, end_partition: int, arena=None,
+                 records=None):
         self.manager = manager
         self.handle = handle
         self.start_partition = start_partition
         self.end_partition = end_partition
         self.fetcher = FetcherIterator(manager, handle,
                                        start_partition, end_partition,
-                                       arena=arena)
+                                       arena=arena, records=records)
 
     def __iter__(self):
         return iter(self.fetcher)

@@ -179,21 +179,35 @@ class TeraSort:
         per = self.ppe // H
         spans = [(lo + h * per, lo + (h + 1) * per - 1) for h in range(H)]
         arenas = self._arenas(H)
-        readers = [eng.manager.get_reader(handle, a, b, arena=ar)
-                   for (a, b), ar in zip(spans, arenas)]
+        if self.wide:
+            # record spec: local one-sided fetches run as the fused copy +
+            # pair-extract kernel and fill each chunk's pair buffer as the
+            # records land (the chunks fetch concurrently: one buffer each)
+            Wb = self.RECORD_BYTES
+            pair_bufs = [self._sort_tmp(2 * (ar.numel() // Wb) + 16,
+                                        self._pairs_attr(h))
+                         for h, ar in enumerate(arenas)]
+            readers = [eng.manager.get_reader(handle, a, b, arena=ar,
+                                              records=(Wb, 10, pb))
+                       for (a, b), ar, pb in zip(spans, arenas, pair_bufs)]
+        else:
+            readers = [eng.manager.get_reader(handle, a, b, arena=ar)
+                       for (a, b), ar in zip(spans, arenas)]
         t_fetch_total = 0.0
         t_sort_total = 0.0
         outs = []
         remote = 0
         chunk_shared_bits = (self.R // per - 1).bit_length()
-        for (chunk_lo, _chunk_hi), reader in zip(spans, readers):
+        for h, ((chunk_lo, _chunk_hi), reader) in enumerate(
+                zip(spans, readers)):
             tf = time.perf_counter()
             if self.wide:
-                # drive the iterator OURSELVES: each fetched chunk's pair
-                # extraction launches as the chunk lands, overlapping the
-                # remaining fetches (collect_partitions is not needed —
-                # the arena holds everything)
-                pre_extracted = self._extract_while_fetching(reader)
+                # drive the iterator OURSELVES: pairs of fetches the fused
+                # lane did not serve are extracted as each chunk lands,
+                # overlapping the remaining fetches (collect_partitions is
+                # not needed — the arena holds everything)
+                pre_extracted = self._extract_while_fetching(
+                    reader, self._pairs_attr(h))
                 parts = None
             else:
                 parts = reader.collect_partitions()
@@ -207,7 +221,7 @@ class TeraSort:
                     arena, self.RECORD_BYTES, key_bytes=10,
                     end_bit=64 - chunk_shared_bits,
                     out=self._rec_out(arena.numel()),
-                    pairs=self._sort_tmp(2 * nrec, "_pairs_cache"),
+                    pairs=self._sort_tmp(2 * nrec, self._pairs_attr(h)),
                     tmp=self._sort_tmp(2 * nrec, "_tmp_cache"),
                     ws=self._sort_ws(),
                     pairs_filled=pre_extracted)
@@ -258,12 +272,19 @@ class TeraSort:
                                  for _ in range(H)]
         return self._arena_cache
 
-    def _extract_while_fetching(self, reader) -> bool:
-        """Iterate the fetcher, launching the (prefix, aux) pair
-        extraction for each CONTIGUOUS landed run — the extract overlaps
+    @staticmethod
+    def _pairs_attr(h: int) -> str:
+        return "_pairs_cache" if h == 0 else f"_pairs_cache{h}"
+
+    def _extract_while_fetching(self, reader,
+                                pairs_attr: str = "_pairs_cache") -> bool:
+        """Iterate the fetcher. Blocks whose fetch ran as the fused kernel
+        already have their pairs; for every other CONTIGUOUS landed run
+        the (prefix, aux) pair extraction is launched here — it overlaps
         the in-flight fetches instead of re-reading the full arena
-        afterwards. Returns True when every byte was covered (else the
-        caller extracts in one pass — growth/non-tensor fallback)."""
+        afterwards. Every record's pair is written exactly once. Returns
+        True when every byte was covered (else the caller extracts in one
+        pass — growth/non-tensor fallback)."""
         import torch
         from ..ops import load
         hs = load()
@@ -276,7 +297,7 @@ class TeraSort:
             return False
         base = buf.data_ptr()
         cap = buf.numel()
-        pairs_buf = self._sort_tmp(2 * (cap // W) + 16, "_pairs_cache")
+        pairs_buf = self._sort_tmp(2 * (cap // W) + 16, pairs_attr)
         stream = torch.cuda.current_stream().cuda_stream
         ok = True
         covered = 0
@@ -303,6 +324,9 @@ class TeraSort:
             nb = view.numel()
             if not (0 <= boff and boff + nb <= cap):
                 ok = False
+                continue
+            if f.pairs_written(boff, nb):
+                covered += nb    # the fused fetch wrote these pairs
                 continue
             if boff == run_off + run_len:
                 run_len += nb
