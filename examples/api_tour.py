@@ -103,7 +103,35 @@ def main():
         print(f"map-side combine: 50000 rows in, {shipped} rows shipped, "
               f"{len(uk)} keys out")
 
-        # 5) metrics: the task/executor counters the reference feeds Spark
+        # 5) sampled range partitioning: split points from the data ------
+        # skewed keys (most of them small) overload the first partitions
+        # of uniform(8); bounds taken from a sample balance them. On an
+        # MI355X box the write is the GPU lane: the split points are
+        # searched by the extract_pairs_bounds kernel (func 4).
+        skewed = (rng.random(50_000) ** 4 * 2.0**64).astype(np.uint64)
+        part = RangePartitioner.from_sample(rng.choice(skewed, 4096), 8)
+        assert part.gpu_params() == (4, 0, 8)
+        handle = eng.register_shuffle(num_maps=1, num_partitions=8)
+        writer = mgr.get_writer(handle, map_id=0)
+        if mgr.gpu is not None:
+            import torch
+            writer.write_device_batch(
+                torch.from_numpy(skewed.view(np.int64)).cuda())
+        else:
+            writer.write_batch(skewed)
+        writer.stop(True, partitioner=part)
+        want = np.bincount(part.partition_ids(skewed), minlength=8)
+        parts = mgr.get_reader(handle, 0, 7).collect_partitions()
+        sizes = [sum((c.numel() if hasattr(c, "numel") else len(c)) // 8
+                     for c in parts[p]) for p in sorted(parts)]
+        assert sizes == want.tolist()
+        uni = np.bincount(RangePartitioner.uniform(8).partition_ids(skewed),
+                          minlength=8)
+        eng.unregister_shuffle(handle)
+        print(f"sampled bounds: keys per partition = {sizes} "
+              f"(uniform bounds: {uni.tolist()})")
+
+        # 6) metrics: the task/executor counters the reference feeds Spark
         print("lifetime:", mgr.lifetime_metrics.format())
 
 

@@ -23,7 +23,8 @@ def ext_path() -> str:
 
 def sources():
     return [os.path.join(CSRC, f) for f in ("pool.cpp", "kernels.hip",
-                                            "reduce.hip", "bindings.cpp")]
+                                            "reduce.hip", "bounds.hip",
+                                            "bindings.cpp")]
 
 
 def needs_build() -> bool:

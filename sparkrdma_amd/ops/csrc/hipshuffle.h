@@ -131,4 +131,12 @@ void reduce_by_key_emit(uintptr_t pairs, uint32_t n, int op, uintptr_t ws,
                         uintptr_t out_keys, uintptr_t out_vals,
                         uintptr_t stream);
 
+// bounds.hip — pair extraction with the partition id in pair.x, found by
+// searching `nbounds` ascending u64 split points (device memory):
+// x = #{bounds <= key prefix}, unsigned; aux as extract_pairs writes it.
+void extract_pairs_bounds(uintptr_t recs, uint64_t n, uint32_t rec_bytes,
+                          uint32_t key_bytes, uintptr_t pairs,
+                          uintptr_t bounds, uint32_t nbounds,
+                          uintptr_t stream, uint64_t idx_base = 0);
+
 }  // namespace hipshuffle

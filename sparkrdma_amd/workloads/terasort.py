@@ -17,6 +17,13 @@ per-executor dataset:
 
 Output invariant (validated): concatenated partitions are globally sorted
 and are a permutation of the input.
+
+``key_skew`` > 0 draws keys as u^(1+key_skew) * 2^64 (u uniform in [0,1)),
+which piles them up at the low end of the key space; the uniform
+partitioner then sends most records to a few partitions.
+``partitioner="sampled"`` is TeraSort's own answer: split points from a
+key sample (partitioner.sample_bounds), searched on the GPU write path.
+Its partitions share no top bits, so the reduce sorts all 64 prefix bits.
 """
 
 from __future__ import annotations
@@ -58,7 +65,8 @@ class TeraSort:
                  partitions_per_executor: int = 64,
                  device: str = "cpu", mode: str = "framework",
                  validate: bool = False, seed: int = 0,
-                 record_bytes: int = 16):
+                 record_bytes: int = 16, key_skew: float = 0.0,
+                 partitioner: str = "uniform"):
         self.engine = engine
         self.n = records_per_executor
         self.device = device
@@ -73,9 +81,20 @@ class TeraSort:
         R = W * partitions_per_executor
         if R & (R - 1):
             raise ValueError("world_size * partitions_per_executor must be pow2")
+        if partitioner not in ("uniform", "sampled"):
+            raise ValueError("partitioner must be 'uniform' or 'sampled'")
+        if partitioner == "sampled" and mode == "rccl":
+            raise ValueError("partitioner='sampled' needs the framework "
+                             "shuffle (mode='rccl' splits by top key bits)")
+        if key_skew < 0:
+            raise ValueError("key_skew must be >= 0")
         self.R = R
         self.ppe = partitions_per_executor
-        self.part = RangePartitioner.uniform(R)
+        self.partitioner = partitioner
+        self.seed = seed
+        # sampled: built collectively on first use (_ensure_partitioner)
+        self.part = (RangePartitioner.uniform(R)
+                     if partitioner == "uniform" else None)
         self.low_bits = 64 - (R - 1).bit_length()
         rank = engine.rank
         if self.wide:
@@ -86,6 +105,9 @@ class TeraSort:
             # 8 bytes mirror the prefix for integrity validation
             recs = torch.randint(-128, 128, (self.n, Wb), dtype=torch.int8,
                                  device="cuda", generator=g)
+            if key_skew > 0:
+                recs[:, :8] = self._skewed_keys_cuda(g, key_skew) \
+                    .view(torch.int8).reshape(self.n, 8)
             prefix = recs[:, :8]
             recs[:, 10:18] = prefix   # integrity mirror
             self.recs = recs.view(torch.uint8).reshape(-1)
@@ -93,18 +115,52 @@ class TeraSort:
         elif device == "cuda":
             import torch
             g = torch.Generator(device="cuda").manual_seed(seed * 1000 + rank)
-            self.keys = torch.randint(-2**63, 2**63 - 1, (self.n,),
-                                      dtype=torch.int64, device="cuda",
-                                      generator=g)
+            if key_skew > 0:
+                self.keys = self._skewed_keys_cuda(g, key_skew)
+            else:
+                self.keys = torch.randint(-2**63, 2**63 - 1, (self.n,),
+                                          dtype=torch.int64, device="cuda",
+                                          generator=g)
             self.vals = self.keys.clone()  # payload := key bytes (integrity)
         else:
             rng = np.random.default_rng(seed * 1000 + rank)
-            self.keys = rng.integers(0, 2**64, self.n, dtype=np.uint64)
+            if key_skew > 0:
+                self.keys = (rng.random(self.n) ** (1.0 + key_skew)
+                             * 2.0 ** 64).astype(np.uint64)
+            else:
+                self.keys = rng.integers(0, 2**64, self.n, dtype=np.uint64)
             self.vals = self.keys.view(np.uint8).reshape(-1, 8).copy()
 
+    #: keys each rank contributes to the sampled partitioner's bounds
+    SAMPLE_PER_RANK = 16384
+
+    def _skewed_keys_cuda(self, g, key_skew: float):
+        """u^(1+key_skew) * 2^64 as u64 bits in an int64 device tensor."""
+        import torch
+        f = torch.rand(self.n, dtype=torch.float64, device="cuda",
+                       generator=g) ** (1.0 + key_skew) * 2.0 ** 64
+        top = f >= 2.0 ** 63       # u64 values with the sign bit set
+        lo = torch.where(top, f - 2.0 ** 63, f).to(torch.int64)
+        return torch.where(top, lo + (-2 ** 63), lo)
+
+    def _ensure_partitioner(self) -> None:
+        """Collective (every rank calls it in the same step): derive the
+        sampled partitioner's bounds from a sample of all ranks' keys."""
+        if self.part is not None:
+            return
+        from ..partitioner import sample_bounds
+        if self.wide:
+            import torch
+            keys = self.recs.view(self.n, self.RECORD_BYTES)[:, :8] \
+                .contiguous().view(torch.int64).reshape(-1)
+        else:
+            keys = self.keys
+        self.part = sample_bounds(self.engine, keys, self.R,
+                                  self.SAMPLE_PER_RANK, self.seed)
     # ------------------------------------------------------------------
 
     def run_step(self) -> TeraSortResult:
+        self._ensure_partitioner()
         if self.mode == "rccl":
             return self._step_rccl()
         if self.mode == "shuffleread":
@@ -197,7 +253,9 @@ class TeraSort:
         t_sort_total = 0.0
         outs = []
         remote = 0
-        chunk_shared_bits = (self.R // per - 1).bit_length()
+        # a sampled partitioner's ranges share no top key bits
+        chunk_shared_bits = ((self.R // per - 1).bit_length()
+                             if self.partitioner == "uniform" else 0)
         for h, ((chunk_lo, _chunk_hi), reader) in enumerate(
                 zip(spans, readers)):
             tf = time.perf_counter()
@@ -213,6 +271,8 @@ class TeraSort:
                 parts = reader.collect_partitions()
             ts_ = time.perf_counter()
             arena = getattr(reader.fetcher, "arena", None)
+            if self.device == "cuda" and arena is not None:
+                self._check_chunk_fits(arena.numel(), h)
             if self.wide and arena is not None:
                 import torch
                 from ..ops.radix import sort_records
@@ -271,6 +331,22 @@ class TeraSort:
                                              device="cuda")
                                  for _ in range(H)]
         return self._arena_cache
+
+    def _check_chunk_fits(self, nbytes: int, h: int) -> None:
+        """A fetch arena that overflows grows (reader), but the sort
+        workspace is sized once for 1.25x the per-executor records
+        (_sort_ws): a chunk past that is a partitioning failure, reported
+        as one instead of as a bare workspace assertion in the sort."""
+        cap = int(self.n * 1.25) + 4096
+        nrec = nbytes // self.RECORD_BYTES
+        if nrec > cap:
+            raise RuntimeError(
+                f"reduce chunk {h} of rank {self.engine.rank} received "
+                f"{nrec} records, more than the {cap} the sort workspace "
+                f"holds (1.25x the {self.n} records per executor): the "
+                f"{self.partitioner!r} partitioner does not balance these "
+                "keys" + (" — use partitioner='sampled'"
+                          if self.partitioner == "uniform" else ""))
 
     @staticmethod
     def _pairs_attr(h: int) -> str:

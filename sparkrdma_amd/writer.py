@@ -31,6 +31,7 @@ import numpy as np
 
 from .manager import ShuffleHandle, ShuffleManager
 from .map_output import make_key
+from .partitioner import GPU_PART_BOUNDS as PART_BOUNDS
 from .stats import TaskMetrics
 
 HEADER_W = 8  # bytes per key
@@ -264,8 +265,9 @@ class ShuffleWriter:
     def _gpu_part_params(self, partitioner):
         """(func, shift, nparts, nbits_eff) for the kernel-side partition
         function (partitioner.gpu_params()): pow2 R via bit extraction,
-        arbitrary R via mulhi-range / hash-mod. One kernel pass covers
-        nbits <= 12; larger R runs the two-level pid radix
+        arbitrary R via mulhi-range / hash-mod / a search of the
+        partitioner's split points (func 4, record lane only). One kernel
+        pass covers nbits <= 12; larger R runs the two-level pid radix
         (_group_pairs_2level), capped at 2^24."""
         R = self.handle.num_partitions
         nbits = max((R - 1).bit_length(), 1)
@@ -280,8 +282,9 @@ class ShuffleWriter:
             params = (0, partitioner.gpu_shift, 0)
         if params is None:
             raise ValueError(
-                f"partitioner {partitioner!r} has no GPU dispatch "
-                "(gpu_params() returned None) — use the CPU write path")
+                f"partitioner {partitioner!r} has no GPU dispatch (no "
+                "gpu_params(), or it returned None) — use the CPU write "
+                "path")
         func, shift, nparts = params
         return func, shift, nparts, min(max(nbits, 4), 12)
 
@@ -320,10 +323,14 @@ class ShuffleWriter:
             keys, vals = reduce_by_key_aos(pr, combiner)
             if vals.dtype != torch.int64:
                 vals = vals.view(torch.int64)
-        if (R - 1).bit_length() > 12:
+        func, shift, nparts, nbits_eff = self._gpu_part_params(partitioner)
+        if (R - 1).bit_length() > 12 or func == PART_BOUNDS:
             # > 4096 partitions: route through the wide-record two-level
             # pid radix (records = the interleaved 16-B AoS pairs, or the
-            # bare keys when value-less)
+            # bare keys when value-less). Split-point partitioners take
+            # the record lane at every R: the direct scatter below derives
+            # its digit from the key twice (hist, scatter) and has no
+            # place to keep a searched partition id.
             if vals is None:
                 recs = keys.contiguous().view(torch.uint8).reshape(-1)
                 self._record_shape = (8, 8)
@@ -336,7 +343,6 @@ class ShuffleWriter:
                 self._record_shape = (16, 8)
             self._gpu_records = [recs]
             return self._commit_gpu_records(partitioner)
-        func, shift, nparts, nbits_eff = self._gpu_part_params(partitioner)
         has_val = vals is not None
         n = keys.numel()
         if n == 0:
@@ -450,13 +456,14 @@ class ShuffleWriter:
         mgr.publish_map_output(self.handle, self.map_id, table_addr)
 
     def _group_pairs_2level(self, hs, recs, n, W, key_bytes, R,
-                            func, shift, nparts, dev, stream):
+                            func, shift, nparts, dev, stream, bounds=None):
         """> 4096 partitions: the single radix pass is capped at 2^12 LDS
         digits, so the PARTITION ID itself is radixed in two levels —
         extract (pid, aux) pairs, scatter by pid>>12 (coarse), then per
         coarse bucket by pid&4095 (fine). Returns (full R counts, pairs,
         grouped pairs, gather digit params: pid is pair.x so the gather
-        recomputes it as plain bits)."""
+        recomputes it as plain bits). ``bounds`` (device split points,
+        func 4) selects the splitter-search extract."""
         import torch
         nbits = (R - 1).bit_length()
         if nbits > 24:
@@ -466,8 +473,14 @@ class ShuffleWriter:
         nbits_c = max((G - 1).bit_length(), 4)
         ndc = 1 << nbits_c
         pairs = torch.empty(2 * n, dtype=torch.int64, device=dev)
-        hs.extract_pairs(recs.data_ptr(), n, W, key_bytes, pairs.data_ptr(),
-                         stream, func, shift, mask_full, nparts)
+        if bounds is not None:
+            hs.extract_pairs_bounds(recs.data_ptr(), n, W, key_bytes,
+                                    pairs.data_ptr(), bounds.data_ptr(),
+                                    bounds.numel(), stream)
+        else:
+            hs.extract_pairs(recs.data_ptr(), n, W, key_bytes,
+                             pairs.data_ptr(), stream, func, shift,
+                             mask_full, nparts)
         hist = torch.empty(hs.radix_hist_bytes(n, 12) // 4,
                            dtype=torch.int32, device=dev)
         scan_ws = torch.empty(hs.radix_scan_ws_bytes(n, 12) // 4,
@@ -557,17 +570,34 @@ class ShuffleWriter:
         dev = recs.device
         stream = torch.cuda.current_stream().cuda_stream
         two_level = (R - 1).bit_length() > 12
+        # split-point partitioner: the extract searches the bounds and
+        # leaves the partition id in pair.x
+        bounds = (partitioner.gpu_bounds(dev) if func == PART_BOUNDS
+                  else None)
+        if bounds is not None and bounds.numel() != R - 1:
+            # an id >= R would have no destination block
+            raise ValueError(
+                f"partitioner has {bounds.numel()} split points, the "
+                f"shuffle was registered with {R} partitions")
         if two_level:
             counts_nd, pairs, pairs_out, gfunc, gshift, gmask, gnparts = \
                 self._group_pairs_2level(hs, recs, n, W, key_bytes, R,
-                                         func, shift, nparts, dev, stream)
+                                         func, shift, nparts, dev, stream,
+                                         bounds)
             nd = R
         else:
             nd = 1 << nbits_eff
-            gfunc, gshift, gmask, gnparts = func, shift, nd - 1, nparts
             pairs = torch.empty(2 * n, dtype=torch.int64, device=dev)
-            hs.extract_pairs(recs.data_ptr(), n, W, key_bytes,
-                             pairs.data_ptr(), stream)
+            if bounds is not None:
+                hs.extract_pairs_bounds(recs.data_ptr(), n, W, key_bytes,
+                                        pairs.data_ptr(), bounds.data_ptr(),
+                                        bounds.numel(), stream)
+                # hist / scatter / gather read the pid as plain bits
+                func, shift, nparts = 0, 0, 0
+            else:
+                hs.extract_pairs(recs.data_ptr(), n, W, key_bytes,
+                                 pairs.data_ptr(), stream)
+            gfunc, gshift, gmask, gnparts = func, shift, nd - 1, nparts
             hist = torch.empty(hs.radix_hist_bytes(n, nbits_eff) // 4,
                                dtype=torch.int32, device=dev)
             scan_ws = torch.empty(hs.radix_scan_ws_bytes(n, nbits_eff) // 4,
