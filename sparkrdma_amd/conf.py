@@ -101,11 +101,15 @@ class ShuffleConf:
     tcp_chunk_size: int = 4 << 20     # streaming chunk (pinned D2H unit)
     # wide-record readers that pass a record spec: which one-sided fetches
     # run as the fused copy + pair-extract kernel instead of a plain copy
-    #   local: sources owned by this executor (default)
+    #   inplace: as local, and a reader opened with in_place=True does not
+    #          copy such a fetch at all — the kernel only extracts the
+    #          pairs, the records stay in this executor's blocks and the
+    #          consumer reads them through record_segments() (default)
+    #   local: sources owned by this executor
     #   host:  also peer executors' slabs on this host (a compute-kernel
     #          copy over xGMI instead of hipMemcpyAsync)
     #   off:   none — every fetch is a plain copy, pairs extracted after
-    fused_record_fetch: str = "local"
+    fused_record_fetch: str = "inplace"
 
     def __post_init__(self) -> None:
         self._validate_range("recv_queue_depth", self.recv_queue_depth, 16, 1 << 20)
@@ -120,9 +124,9 @@ class ShuffleConf:
         if self.transport not in ("auto", "shm", "ipc", "rccl", "tcp"):
             raise ConfError(
                 f"transport must be auto|shm|ipc|rccl|tcp, got {self.transport!r}")
-        if self.fused_record_fetch not in ("local", "host", "off"):
+        if self.fused_record_fetch not in ("inplace", "local", "host", "off"):
             raise ConfError(
-                "fusedRecordFetch must be local|host|off, got "
+                "fusedRecordFetch must be inplace|local|host|off, got "
                 f"{self.fused_record_fetch!r}")
 
     @staticmethod

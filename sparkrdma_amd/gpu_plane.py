@@ -310,6 +310,23 @@ class GpuDataPlane:
             peer, [dst_ptr], [base + addr], [length], rec_bytes, key_bytes,
             [pairs_ptr], [idx_base])
 
+    def issue_extract_records(self, key: int, addr: int, length: int,
+                              rec_bytes: int, key_bytes: int,
+                              pairs_ptr: int, idx_base: int) -> tuple:
+        """The in-place counterpart of ``issue_read_records_into``: the
+        run's pairs are written as there, the records are NOT copied
+        (kernels.hip extract_records). Returns ``(event id, device pointer
+        of the run)``; the pointer is into the block's slab and stays valid
+        until the shuffle that owns the block is unregistered."""
+        exec_id, _ = split_key(key)
+        self.hs.set_device(self.device)
+        src = self.resolve(key) + addr
+        peer = self._stream_slot(exec_id)
+        ev = self.hs.extract_records_batch(
+            peer, [src], [length], rec_bytes, key_bytes, [pairs_ptr],
+            [idx_base])
+        return ev, src
+
     def _stream_slot(self, exec_id: int) -> int:
         """Copy-stream selector: the peer's GPU ordinal — streams map to
         xGMI links, not executor ids."""

@@ -308,12 +308,15 @@ class ShuffleManager:
         return ShuffleWriter(self, handle, map_id)
 
     def get_reader(self, handle: ShuffleHandle, start_partition: int,
-                   end_partition: int, arena=None, records=None):
+                   end_partition: int, arena=None, records=None,
+                   in_place: bool = False):
         """``records``: optional wide-record spec ``(rec_bytes, key_bytes,
-        pairs_tensor)`` — see FetcherIterator."""
+        pairs_tensor)``; ``in_place``: the consumer takes the records
+        through ``fetcher.record_segments()`` and not through
+        ``fetcher.arena`` — see FetcherIterator."""
         from .reader import ShuffleReader
         return ShuffleReader(self, handle, start_partition, end_partition,
-                             arena=arena, records=records)
+                             arena=arena, records=records, in_place=in_place)
 
     def unregister_shuffle(self, shuffle_id: int, notify_driver: bool = True) -> None:
         # release served blocks (liveness discipline: blocks stay alive until

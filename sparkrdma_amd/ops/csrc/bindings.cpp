@@ -39,6 +39,13 @@ PYBIND11_MODULE(_hipshuffle, m) {
         py::arg("dsts"), py::arg("srcs"), py::arg("sizes"),
         py::arg("rec_bytes"), py::arg("key_bytes"), py::arg("pairs_ptrs"),
         py::arg("idx_bases"), py::call_guard<py::gil_scoped_release>());
+  m.def("extract_records_batch", &hs::extract_records_batch_ids,
+        py::arg("peer"), py::arg("srcs"), py::arg("sizes"),
+        py::arg("rec_bytes"), py::arg("key_bytes"), py::arg("pairs_ptrs"),
+        py::arg("idx_bases"), py::call_guard<py::gil_scoped_release>());
+  m.def("extract_records", &hs::extract_records, py::arg("src"), py::arg("n"),
+        py::arg("rec_bytes"), py::arg("key_bytes"), py::arg("pairs"),
+        py::arg("idx_base") = 0, py::arg("stream") = 0);
   m.def("fetch_block_records", &hs::fetch_block_records);
   m.def("poll_event", &hs::poll_event,
         py::call_guard<py::gil_scoped_release>());
@@ -83,7 +90,8 @@ PYBIND11_MODULE(_hipshuffle, m) {
         py::arg("pairs"), py::arg("n"), py::arg("rec_bytes"),
         py::arg("dst_mode"), py::arg("out_base"), py::arg("dst_addr") = 0,
         py::arg("dstart") = 0, py::arg("shift") = 0, py::arg("mask") = 0,
-        py::arg("func") = 0, py::arg("nparts") = 0, py::arg("stream") = 0);
+        py::arg("func") = 0, py::arg("nparts") = 0, py::arg("stream") = 0,
+        py::arg("segs") = 0, py::arg("nsegs") = 0);
   m.def("onesweep_sort_aos_word_u64", &hs::onesweep_sort_aos_word_u64,
         py::arg("pairs"), py::arg("tmp_pairs"), py::arg("n"),
         py::arg("start_bit"), py::arg("end_bit"), py::arg("ws"),
@@ -94,6 +102,7 @@ PYBIND11_MODULE(_hipshuffle, m) {
         py::arg("start_bit"), py::arg("end_bit"), py::arg("ws"),
         py::arg("stream") = 0, py::arg("sort_word") = 0,
         py::arg("recs") = 0, py::arg("out") = 0, py::arg("rec_bytes") = 0,
+        py::arg("segs") = 0, py::arg("nsegs") = 0,
         py::call_guard<py::gil_scoped_release>());
   m.def("sort_workspace_bytes", &hs::sort_workspace_bytes);
   m.def("sort_pairs_u64", &hs::sort_pairs_u64, py::arg("keys"),
@@ -132,8 +141,8 @@ PYBIND11_MODULE(_hipshuffle, m) {
         py::arg("pairs"), py::arg("tmp_pairs"), py::arg("n"),
         py::arg("end_bit"), py::arg("key_bytes"), py::arg("ws"),
         py::arg("stream"), py::arg("recs"), py::arg("out"),
-        py::arg("rec_bytes"), py::arg("fuse") = 1,
-        py::call_guard<py::gil_scoped_release>());
+        py::arg("rec_bytes"), py::arg("fuse") = 1, py::arg("segs") = 0,
+        py::arg("nsegs") = 0, py::call_guard<py::gil_scoped_release>());
   m.def("onesweep_sort_aos7_u64", &hs::onesweep_sort_aos7_u64,
         py::arg("pairs"), py::arg("tmp_pairs"), py::arg("n"),
         py::arg("start_bit"), py::arg("end_bit"), py::arg("ws"),

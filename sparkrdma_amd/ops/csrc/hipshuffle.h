@@ -28,6 +28,14 @@ uint64_t read_records_batch_ids(int peer, const std::vector<uintptr_t>& dsts,
                                 uint32_t rec_bytes, uint32_t key_bytes,
                                 const std::vector<uintptr_t>& pairs_ptrs,
                                 const std::vector<uint64_t>& idx_bases);
+// the in-place counterpart: extract_records per (src, size), nothing is
+// copied; same streams, same checks, one completion event
+uint64_t extract_records_batch_ids(int peer,
+                                   const std::vector<uintptr_t>& srcs,
+                                   const std::vector<size_t>& sizes,
+                                   uint32_t rec_bytes, uint32_t key_bytes,
+                                   const std::vector<uintptr_t>& pairs_ptrs,
+                                   const std::vector<uint64_t>& idx_bases);
 bool poll_event(uint64_t id);
 void wait_event(uint64_t id);
 int64_t tcp_recv_chunks(int fd, uintptr_t out, uint64_t total);
@@ -54,15 +62,26 @@ void extract_pairs(uintptr_t recs, uint64_t n, uint32_t rec_bytes,
                    int pid_func = -1, int pid_shift = 0,
                    uint32_t pid_mask = 0, uint32_t pid_nparts = 0,
                    uint64_t idx_base = 0);
+// segs / nsegs (here and in the fused sorts below): a device table of
+// {u64 first_rec, const u32* base} entries sorted by first_rec and covering
+// every record index; record idx is read at
+// base[s] + (idx - first_rec[s]) * rec_bytes for the last s with
+// first_rec[s] <= idx. nsegs == 0: contiguous from `recs`.
 void gather_records(uintptr_t recs, uintptr_t pairs, uint64_t n,
                     uint32_t rec_bytes, int dst_mode, uint64_t out_base,
                     uintptr_t dst_addr, uintptr_t dstart, int shift,
                     uint32_t mask, int func, uint32_t nparts,
-                    uintptr_t stream);
+                    uintptr_t stream, uintptr_t segs = 0,
+                    uint32_t nsegs = 0);
 uint32_t fetch_block_records(uint32_t rec_bytes);
 void fetch_records(uintptr_t dst, uintptr_t src, uint64_t n,
                    uint32_t rec_bytes, uint32_t key_bytes, uintptr_t pairs,
                    uint64_t idx_base, uintptr_t stream);
+// fetch_records without the copy: the pairs of the n records at src, which
+// stay where they are
+void extract_records(uintptr_t src, uint64_t n, uint32_t rec_bytes,
+                     uint32_t key_bytes, uintptr_t pairs, uint64_t idx_base,
+                     uintptr_t stream);
 size_t sort_workspace_bytes(uint32_t n);
 int sort_pairs_u64(uintptr_t keys, uintptr_t vals, uintptr_t tmp_keys,
                    uintptr_t tmp_vals, uint32_t n, int start_bit, int end_bit,
@@ -100,7 +119,8 @@ int onesweep_sort_aos_fused_u64(uintptr_t pairs, uintptr_t tmp_pairs,
                                 uint32_t n, int start_bit, int end_bit,
                                 uintptr_t ws, uintptr_t stream,
                                 int sort_word, uintptr_t recs,
-                                uintptr_t out, uint32_t rec_bytes);
+                                uintptr_t out, uint32_t rec_bytes,
+                                uintptr_t segs = 0, uint32_t nsegs = 0);
 // truncated wide-record sort with tie repair (kernels.hip)
 void set_tie_repair(int m);
 int last_sort_path();
@@ -112,7 +132,8 @@ int sort_records_truncated_u64(uintptr_t pairs, uintptr_t tmp_pairs,
                                uint32_t n, int end_bit, int key_bytes,
                                uintptr_t ws, uintptr_t stream,
                                uintptr_t recs, uintptr_t out,
-                               uint32_t rec_bytes, int fuse);
+                               uint32_t rec_bytes, int fuse,
+                               uintptr_t segs = 0, uint32_t nsegs = 0);
 int onesweep_sort_pairs_u64(uintptr_t keys, uintptr_t vals,
                             uintptr_t tmp_keys, uintptr_t tmp_vals,
                             uint32_t n, int start_bit, int end_bit,

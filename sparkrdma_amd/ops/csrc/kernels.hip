@@ -415,6 +415,48 @@ struct GatherSlot {
   uint32_t* dst;        // first word of its destination slot
 };
 
+// Where record idx of a pair's aux word lives. Record indices are positions
+// in the reader's (virtual) arena; the records themselves may sit in
+// several places — a reader that takes its local blocks in place leaves
+// them in the shuffle's HBM blocks and copies only the rest into the arena
+// (reader.py record_segments). The caller passes a device table of nsegs
+// entries sorted by first_rec that cover [0, n) without gap or overlap;
+// record idx is record (idx - first_rec) of the LAST entry with
+// first_rec <= idx, counted from that entry's base. nsegs == 0: the
+// records are contiguous from `recs`, the plain address arithmetic, behind
+// a branch that is uniform for the whole grid (nsegs is a kernel argument).
+//
+// The table is searched in global memory: the flagship job has 86 entries,
+// one per fetch (16 bytes each, read by every block, so it stays in L2 and
+// the vector L1; 7 search steps cost its final pass 0.8 %,
+// profiles/r08_inplace_local_records.md), and the search runs once per
+// slot in the staging
+// loops, ahead of the record loads it addresses — copy_record_words never
+// sees it. An LDS copy would cap the table (the fused pass has under 4 KB
+// to spare before it loses its second resident block).
+struct RecSegment {
+  uint64_t first_rec;    // index of the segment's first record
+  const uint32_t* base;  // first word of that record
+};
+
+__device__ __forceinline__ const uint32_t* record_src(
+    const uint32_t* __restrict__ recs, const RecSegment* __restrict__ segs,
+    uint32_t nsegs, uint64_t idx, uint32_t w4) {
+  if (nsegs == 0) return recs + idx * w4;
+  // segs[lo].first_rec <= idx < segs[hi].first_rec (segs[0].first_rec is
+  // 0, hi == nsegs stands for +inf): only entries in [1, nsegs) are read
+  uint32_t lo = 0, hi = nsegs;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (segs[mid].first_rec <= idx)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  const RecSegment s = segs[lo];
+  return s.base + (idx - s.first_rec) * w4;
+}
+
 // independent record loads a lane issues before its first store
 constexpr int GATHER_BATCH = 8;  // 16: no faster, 90 / 160 VGPRs
 
@@ -615,7 +657,10 @@ __attribute__((amdgpu_waves_per_eu(LEAN ? 6 : 1))) void onesweep_pass_kernel(
     uint32_t rec_w4 = 0 /* record words; key_dst then holds per-digit
                            RECORD base addresses and the writeout copies
                            whole records instead of pairs — the final
-                           sort pass IS the gather */) {
+                           sort pass IS the gather */,
+    const RecSegment* __restrict__ rec_segs = nullptr, /* FUSE_GATHER: */
+    uint32_t rec_nsegs = 0 /* record sources (record_src); 0 = contiguous
+                              from rec_words */) {
   constexpr int ND = 1 << PBITS;
   extern __shared__ char smem_raw[];
   constexpr int TILE_T = BS * IT;
@@ -848,7 +893,7 @@ __attribute__((amdgpu_waves_per_eu(LEAN ? 6 : 1))) void onesweep_pass_kernel(
           uint32_t off = (pref[d] + (j - start[d])) & off_mask;
           uint64_t idx = (uint64_t)kv.y & AUX_IDX_MASK;
           slots[j] = GatherSlot{
-              rec_words + idx * rec_w4,
+              record_src(rec_words, rec_segs, rec_nsegs, idx, rec_w4),
               reinterpret_cast<uint32_t*>(key_dst[d]) +
                   (uint64_t)off * rec_w4};
         }
@@ -972,6 +1017,16 @@ __global__ void onesweep_digit_bases_kernel(
 // place a record before its pair exists); the reduce side does not: its
 // one-sided fetch moves every record through registers anyway, and
 // fetch_records_kernel emits the pairs from there.
+// Nor does the reduce side need the records in one buffer: a pair's aux
+// index is a position in the reader's VIRTUAL arena, and both consumers of
+// it — gather_records_kernel and the fused final sort pass — find the
+// record through record_src, a segment table of (first index, address)
+// runs. So blocks this executor owns are not fetched at all: the
+// extract-only variant of fetch_records_kernel reads them once for the
+// pairs and the final pass gathers them from the shuffle's blocks, the
+// same random W-byte reads over the same span it paid on the arena copy
+// (profiles/r08_inplace_local_records.md). Each local record is then
+// moved twice, map write and final pass, not three times.
 
 // Key layout inside a record: bytes [0,8) u64 LE prefix, bytes [8,10)
 // u16 LE low bits (key_bytes == 8 or 10); 80-bit order = (prefix, lo).
@@ -1031,7 +1086,8 @@ __global__ __launch_bounds__(BLOCK) void gather_records_kernel(
     uint32_t recs_per_block /* <= GATHER_MAX_RECS */, int dst_mode,
     uint64_t out_base, const uint64_t* __restrict__ dst_addr,
     const uint32_t* __restrict__ dstart, int shift, uint32_t mask,
-    int func, uint32_t nparts) {
+    int func, uint32_t nparts, const RecSegment* __restrict__ segs,
+    uint32_t nsegs /* record sources (record_src); 0 = contiguous */) {
   __shared__ GatherSlot slots[GATHER_MAX_RECS];
   const uint64_t r0 = (uint64_t)blockIdx.x * recs_per_block;
   if (r0 >= n) return;
@@ -1048,7 +1104,7 @@ __global__ __launch_bounds__(BLOCK) void gather_records_kernel(
       dst = reinterpret_cast<uint32_t*>(dst_addr[d]) +
             (uint64_t)(uint32_t)(j - dstart[d]) * w4;
     }
-    slots[r] = GatherSlot{recs + idx * w4, dst};
+    slots[r] = GatherSlot{record_src(recs, segs, nsegs, idx, w4), dst};
   }
   __syncthreads();
   copy_record_words<BLOCK, GATHER_BATCH>(slots, nr, w4);
@@ -1080,8 +1136,9 @@ void gather_records(uintptr_t recs, uintptr_t pairs, uint64_t n,
                     uint32_t rec_bytes, int dst_mode, uint64_t out_base,
                     uintptr_t dst_addr, uintptr_t dstart, int shift,
                     uint32_t mask, int func, uint32_t nparts,
-                    uintptr_t stream) {
+                    uintptr_t stream, uintptr_t segs, uint32_t nsegs) {
   if (rec_bytes % 4) throw std::runtime_error("rec_bytes % 4 != 0");
+  if (nsegs && !segs) throw std::runtime_error("nsegs without a table");
   auto s = reinterpret_cast<hipStream_t>(stream);
   uint32_t w4 = rec_bytes / 4;
   // ~32k words per block (whole copy batches at W = 100 and 256), at
@@ -1098,7 +1155,8 @@ void gather_records(uintptr_t recs, uintptr_t pairs, uint64_t n,
                      dst_mode, out_base,
                      reinterpret_cast<const uint64_t*>(dst_addr),
                      reinterpret_cast<const uint32_t*>(dstart), shift, mask,
-                     func, nparts);
+                     func, nparts, reinterpret_cast<const RecSegment*>(segs),
+                     nsegs);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -1125,6 +1183,12 @@ void gather_records(uintptr_t recs, uintptr_t pairs, uint64_t n,
 // nothing — so the kernel is equally valid for a peer-mapped source. dst
 // gets exactly [dst, dst + n * w4), pairs exactly [pairs, pairs + 2n).
 //
+// COPY = false is the in-place variant (extract_records): the same loads
+// and key-table writes, no record store, dst never touched. The reader uses
+// it for blocks this executor owns — copying them from one place in its
+// HBM to another buys nothing, the sort gathers them from where they are
+// (record_src) — and the fetch then moves 0.54x the bytes.
+//
 // Tile: about 4096 words (16 KB, two batches) per block. With src and dst
 // 4 and 12 bytes off a 16-byte boundary, 4 GB of 100-byte records moved at
 // 4.5-4.7 TB/s (records read + written + pairs written) with 1024-record
@@ -1148,7 +1212,7 @@ static inline uint32_t fetch_block_records_w4(uint32_t w4) {
 // as its own body, so neither the loads nor the stores of a whole batch
 // sit behind a per-lane test or a wait that only the tile's last batch
 // needs. (r, o) = record and word-in-record of the lane's next word.
-template <int BS, int U, bool WHOLE>
+template <int BS, int U, bool WHOLE, bool COPY>
 __device__ __forceinline__ void fetch_batch(
     const uint32_t* __restrict__ s, uint32_t* __restrict__ d,
     uint32_t* keytab, uint32_t q0, uint32_t total, uint32_t w4, uint32_t dr,
@@ -1159,11 +1223,19 @@ __device__ __forceinline__ void fetch_batch(
     const uint32_t q = q0 + (uint32_t)u * BS + threadIdx.x;
     v[u] = (WHOLE || q < total) ? s[q] : 0u;
   }
+  // without the store only words 0..2 of a record are used, and the
+  // compiler would sink some of the loads behind that per-lane test: keep
+  // the batch what it is with COPY, U unconditional loads up front (an
+  // empty statement per value, after ALL loads are issued)
+  if (!COPY) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) asm volatile("" : "+v"(v[u]));
+  }
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const uint32_t q = q0 + (uint32_t)u * BS + threadIdx.x;
     if (WHOLE || q < total) {
-      d[q] = v[u];
+      if (COPY) d[q] = v[u];
       if (o < 3) keytab[r * 3 + o] = v[u];
     }
     o += dc;
@@ -1175,7 +1247,7 @@ __device__ __forceinline__ void fetch_batch(
   }
 }
 
-template <int BS, int U>
+template <int BS, int U, bool COPY>
 __global__ __launch_bounds__(BS) void fetch_records_kernel(
     const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, uint64_t n,
     uint32_t w4 /* rec_bytes/4 */,
@@ -1187,7 +1259,7 @@ __global__ __launch_bounds__(BS) void fetch_records_kernel(
   const uint32_t nr = (uint32_t)min((uint64_t)recs_per_block, n - r0);
   const uint32_t total = nr * w4;
   const uint32_t* __restrict__ s = src + r0 * w4;
-  uint32_t* __restrict__ d = dst + r0 * w4;
+  uint32_t* __restrict__ d = COPY ? dst + r0 * w4 : nullptr;
   const uint32_t tid = threadIdx.x;
   const uint32_t dr = BS / w4, dc = BS % w4;
   uint32_t r = tid / w4, o = tid % w4;
@@ -1195,9 +1267,11 @@ __global__ __launch_bounds__(BS) void fetch_records_kernel(
   uint32_t q0 = 0;
 #pragma unroll 1
   for (; q0 < whole_end; q0 += BS * U)
-    fetch_batch<BS, U, true>(s, d, keytab, q0, total, w4, dr, dc, r, o);
+    fetch_batch<BS, U, true, COPY>(s, d, keytab, q0, total, w4, dr, dc, r,
+                                   o);
   if (q0 < total)
-    fetch_batch<BS, U, false>(s, d, keytab, q0, total, w4, dr, dc, r, o);
+    fetch_batch<BS, U, false, COPY>(s, d, keytab, q0, total, w4, dr, dc, r,
+                                    o);
   __syncthreads();
   for (uint32_t j = tid; j < nr; j += BS) {
     const uint64_t prefix =
@@ -1234,11 +1308,43 @@ void fetch_records(uintptr_t dst, uintptr_t src, uint64_t n,
   const uint32_t rpb = fetch_block_records_w4(w4);
   const uint64_t grid = (n + rpb - 1) / rpb;
   if (grid > 0x7FFFFFFF) throw std::runtime_error("grid too large");
-  hipLaunchKernelGGL((fetch_records_kernel<BLOCK, FETCH_BATCH>),
+  hipLaunchKernelGGL((fetch_records_kernel<BLOCK, FETCH_BATCH, true>),
                      dim3((uint32_t)grid), dim3(BLOCK), 0,
                      reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<const uint32_t*>(src),
                      reinterpret_cast<uint32_t*>(dst), n, w4, rpb, key_bytes,
+                     reinterpret_cast<uint64_t*>(pairs), idx_base);
+  HIP_CHECK(hipGetLastError());
+}
+
+// The in-place variant: the same loads and the same key-table writes, no
+// record store — the records stay where they are (a block of this
+// executor's own shuffle output) and the sort gathers them from there
+// through a segment table (record_src). One streaming read of the run.
+void extract_records(uintptr_t src, uint64_t n, uint32_t rec_bytes,
+                     uint32_t key_bytes, uintptr_t pairs, uint64_t idx_base,
+                     uintptr_t stream) {
+  if (rec_bytes % 4 || rec_bytes < 8)
+    throw std::runtime_error("rec_bytes must be a multiple of 4, >= 8");
+  if (key_bytes != 8 && key_bytes != 10)
+    throw std::runtime_error("key_bytes must be 8 or 10");
+  if (key_bytes > 8 && rec_bytes < 12)
+    throw std::runtime_error("key_bytes 10 needs rec_bytes >= 12");
+  if ((n >> 48) || ((idx_base + n) >> 48))
+    throw std::runtime_error("idx_base + n exceeds 2^48");
+  if (src % 4 || pairs % 16)
+    throw std::runtime_error(
+        "extract_records: src needs 4-byte, pairs 16-byte alignment");
+  if (n == 0) return;
+  const uint32_t w4 = rec_bytes / 4;
+  const uint32_t rpb = fetch_block_records_w4(w4);
+  const uint64_t grid = (n + rpb - 1) / rpb;
+  if (grid > 0x7FFFFFFF) throw std::runtime_error("grid too large");
+  hipLaunchKernelGGL((fetch_records_kernel<BLOCK, FETCH_BATCH, false>),
+                     dim3((uint32_t)grid), dim3(BLOCK), 0,
+                     reinterpret_cast<hipStream_t>(stream),
+                     reinterpret_cast<const uint32_t*>(src),
+                     static_cast<uint32_t*>(nullptr), n, w4, rpb, key_bytes,
                      reinterpret_cast<uint64_t*>(pairs), idx_base);
   HIP_CHECK(hipGetLastError());
 }
@@ -1665,8 +1771,15 @@ static int onesweep_sort_tmpl(uintptr_t keys, uintptr_t vals,
                               uint32_t fuse_rec_bytes = 0,
                               uint64_t tie_run_mask = 0,
                               uint64_t tie_lo_mask = 0,
-                              uint32_t* tie_flag = nullptr) {
+                              uint32_t* tie_flag = nullptr,
+                              uintptr_t fuse_segs = 0,
+                              uint32_t fuse_nsegs = 0) {
   constexpr int PD = 1 << PBITS;
+  // fusion is asked for by naming a record source: fuse_recs, or a
+  // segment table (record_src), with which fuse_recs is unused and may be 0
+  const bool want_fuse = fuse_recs || fuse_nsegs;
+  if (fuse_nsegs && !fuse_segs)
+    throw std::runtime_error("fused sort: nsegs without a table");
   const int aos_tile = g_aos_tile;
   uint32_t nb = aos ? os_num_tiles_t(n, aos_tile) : os_num_tiles(n);
   int passes = (end_bit - start_bit + PBITS - 1) / PBITS;
@@ -1727,7 +1840,7 @@ static int onesweep_sort_tmpl(uintptr_t keys, uintptr_t vals,
     // (the gather folded into the sort — key_dst becomes record bases)
     // (not in hist+scan mode: the fused kernel walks lookback descriptors,
     // which that mode never resets — the caller falls back via -1)
-    const bool fuse = fuse_recs && p == passes - 1 && aos &&
+    const bool fuse = want_fuse && p == passes - 1 && aos &&
                       aos_tile == 4096 && g_split_exch <= 1 && !g_lean &&
                       !want_hist;
     if (use_hist) {
@@ -1764,7 +1877,8 @@ static int onesweep_sort_tmpl(uintptr_t keys, uintptr_t vals,
           ticket, key_dst, val_dst, g_pass_stage, nullptr, nullptr,
           sort_word, g_lb_mode, 0,
           reinterpret_cast<const uint32_t*>(fuse_recs),
-          fuse_rec_bytes / 4);
+          fuse_rec_bytes / 4,
+          reinterpret_cast<const RecSegment*>(fuse_segs), fuse_nsegs);
       HIP_CHECK(hipGetLastError());
       return cur;  // records land in fuse_out; pair buffers are dead
     } else if (aos && aos_tile == 8192) {
@@ -1816,7 +1930,7 @@ static int onesweep_sort_tmpl(uintptr_t keys, uintptr_t vals,
   }
   // a requested fusion that no pass applied (non-default tile/ablation
   // modes) must NOT silently leave `out` unwritten — caller falls back
-  if (fuse_recs) return -1;
+  if (want_fuse) return -1;
   return cur;
 }
 
@@ -1850,15 +1964,18 @@ int onesweep_sort_aos_word_u64(uintptr_t pairs, uintptr_t tmp_pairs,
 
 // sort + FUSED final gather: records land sorted in `out` (the last
 // pass's writeout copies whole records; the separate gather kernel and
-// the final pair round trip disappear).
+// the final pair round trip disappear). segs / nsegs: where the records
+// are when they are not contiguous from `recs` (record_src).
 int onesweep_sort_aos_fused_u64(uintptr_t pairs, uintptr_t tmp_pairs,
                                 uint32_t n, int start_bit, int end_bit,
                                 uintptr_t ws, uintptr_t stream,
                                 int sort_word, uintptr_t recs,
-                                uintptr_t out, uint32_t rec_bytes) {
+                                uintptr_t out, uint32_t rec_bytes,
+                                uintptr_t segs, uint32_t nsegs) {
   return onesweep_sort_tmpl<8>(pairs, 0, tmp_pairs, 0, n, start_bit, end_bit,
                                ws, reinterpret_cast<hipStream_t>(stream), 1,
-                               sort_word, recs, out, rec_bytes);
+                               sort_word, recs, out, rec_bytes, 0, 0,
+                               nullptr, segs, nsegs);
 }
 
 // ---------------------------------------------------------------------------
@@ -1909,7 +2026,8 @@ int sort_records_truncated_u64(uintptr_t pairs, uintptr_t tmp_pairs,
                                uint32_t n, int end_bit, int key_bytes,
                                uintptr_t ws, uintptr_t stream,
                                uintptr_t recs, uintptr_t out,
-                               uint32_t rec_bytes, int fuse) {
+                               uint32_t rec_bytes, int fuse, uintptr_t segs,
+                               uint32_t nsegs) {
   g_last_sort_path = 0;
   if (end_bit > 64) end_bit = 64;
   if (!fuse || !g_tie_repair || n == 0 || g_aos_tile != 4096 ||
@@ -1928,7 +2046,7 @@ int sort_records_truncated_u64(uintptr_t pairs, uintptr_t tmp_pairs,
   HIP_CHECK(hipMemsetAsync(flag, 0, 4, s));
   int cur = onesweep_sort_tmpl<8>(pairs, 0, tmp_pairs, 0, n, lo_bit, end_bit,
                                   ws, s, 1, 0, recs, out, rec_bytes,
-                                  run_mask, lo_mask, flag);
+                                  run_mask, lo_mask, flag, segs, nsegs);
   if (cur < 0) throw std::runtime_error("truncated sort: fusion refused");
   uint32_t overflow = 0;
   HIP_CHECK(hipMemcpyAsync(&overflow, flag, 4, hipMemcpyDeviceToHost, s));
@@ -1943,7 +2061,8 @@ int sort_records_truncated_u64(uintptr_t pairs, uintptr_t tmp_pairs,
       onesweep_sort_tmpl<8>(pairs, 0, tmp_pairs, 0, n, 48, 64, ws, s, 1, 1))
     std::swap(pairs, tmp_pairs);
   if (onesweep_sort_tmpl<8>(pairs, 0, tmp_pairs, 0, n, 0, end_bit, ws, s, 1,
-                            0, recs, out, rec_bytes) < 0)
+                            0, recs, out, rec_bytes, 0, 0, nullptr, segs,
+                            nsegs) < 0)
     throw std::runtime_error("sort fallback: fusion refused");
   return g_last_sort_path = 2;
 }

@@ -189,6 +189,30 @@ class CopyEngine {
     return signal(s);
   }
 
+  // read_records_batch for blocks the reader takes in place: the pairs
+  // only (kernels.hip extract_records), the records are not moved.
+  uint64_t extract_records_batch(int peer, const std::vector<uintptr_t>& srcs,
+                                 const std::vector<size_t>& sizes,
+                                 uint32_t rec_bytes, uint32_t key_bytes,
+                                 const std::vector<uintptr_t>& pairs_ptrs,
+                                 const std::vector<uint64_t>& idx_bases) {
+    const size_t m = srcs.size();
+    if (sizes.size() != m || pairs_ptrs.size() != m || idx_bases.size() != m)
+      throw std::runtime_error("extract_records_batch: list lengths differ");
+    if (rec_bytes == 0)
+      throw std::runtime_error("extract_records_batch: rec_bytes is 0");
+    for (size_t i = 0; i < m; ++i)
+      if (sizes[i] % rec_bytes)
+        throw std::runtime_error(
+            "extract_records_batch: size is not a whole number of records");
+    hipStream_t s = stream_for(peer);
+    for (size_t i = 0; i < m; ++i)
+      extract_records(srcs[i], sizes[i] / rec_bytes, rec_bytes, key_bytes,
+                      pairs_ptrs[i], idx_bases[i],
+                      reinterpret_cast<uintptr_t>(s));
+    return signal(s);
+  }
+
   // true = complete (event recycled), false = still in flight
   bool poll(uint64_t id) {
     hipEvent_t ev;
@@ -281,6 +305,15 @@ uint64_t read_records_batch_ids(int peer, const std::vector<uintptr_t>& dsts,
                                 const std::vector<uint64_t>& idx_bases) {
   return copy_engine().read_records_batch(peer, dsts, srcs, sizes, rec_bytes,
                                           key_bytes, pairs_ptrs, idx_bases);
+}
+uint64_t extract_records_batch_ids(int peer,
+                                   const std::vector<uintptr_t>& srcs,
+                                   const std::vector<size_t>& sizes,
+                                   uint32_t rec_bytes, uint32_t key_bytes,
+                                   const std::vector<uintptr_t>& pairs_ptrs,
+                                   const std::vector<uint64_t>& idx_bases) {
+  return copy_engine().extract_records_batch(peer, srcs, sizes, rec_bytes,
+                                             key_bytes, pairs_ptrs, idx_bases);
 }
 bool poll_event(uint64_t id) { return copy_engine().poll(id); }
 void wait_event(uint64_t id) { return copy_engine().wait(id); }

@@ -223,13 +223,37 @@ def extract_pairs(recs: torch.Tensor, rec_bytes: int, key_bytes: int = 8,
     return pairs
 
 
-def sort_records(recs: torch.Tensor, rec_bytes: int, key_bytes: int = 8,
+def _segment_table(segments, n: int, rec_bytes: int, device):
+    """``segments`` of sort_records -> (recs pointer, table tensor or None,
+    nsegs, checked triples). The table is the device form the kernels search
+    (hipshuffle.h): int64 [nsegs, 2] rows of (first_rec, device address).
+    One segment needs no table: its address is the contiguous base."""
+    segs = sorted((int(a), int(c), int(p)) for a, c, p in segments if c)
+    pos = 0
+    for first, cnt, ptr in segs:
+        if first != pos:
+            raise ValueError(f"segments leave a gap or overlap at record "
+                             f"{min(first, pos)}")
+        if ptr % 4:
+            raise ValueError("segment address is not 4-byte aligned")
+        pos = first + cnt
+    if pos != n:
+        raise ValueError(f"segments cover {pos} records, expected {n}")
+    if len(segs) == 1:
+        return segs[0][2], None, 0, segs
+    table = torch.tensor([[first, ptr] for first, _cnt, ptr in segs],
+                         dtype=torch.int64, device=device)
+    return 0, table, len(segs), segs
+
+
+def sort_records(recs, rec_bytes: int, key_bytes: int = 8,
                  end_bit: int = 64, out: Optional[torch.Tensor] = None,
                  pairs: Optional[torch.Tensor] = None,
                  tmp: Optional[torch.Tensor] = None,
                  ws: Optional[torch.Tensor] = None,
                  fuse: bool = True,
-                 pairs_filled: bool = False) -> torch.Tensor:
+                 pairs_filled: bool = False,
+                 segments=None) -> torch.Tensor:
     """Sort W-byte AoS records by their 80-bit key: u64 LE prefix at
     offset 0 (bits [0, end_bit) significant — callers whose partitions
     share top prefix bits pass end_bit = 64 - shared) then, for
@@ -240,23 +264,53 @@ def sort_records(recs: torch.Tensor, rec_bytes: int, key_bytes: int = 8,
     full-record passes at W = 100 (kernels.hip 'wide-record machinery').
     Returns the sorted records (a fresh tensor, or ``out``).
 
+    ``segments``: the records are not one contiguous buffer but
+    ``(first_rec, nrec, device_ptr)`` runs, as a reader's
+    ``record_segments()`` returns them: record ``first_rec + i`` is the
+    ``i``-th record at ``device_ptr``. The runs must cover every index
+    exactly once. ``recs`` then only supplies the extent — a uint8 tensor
+    of that many bytes whose contents are never read, or the byte count
+    itself — and pair indices are positions in that virtual buffer, so the
+    output is the one a contiguous copy would give. The memory behind the
+    pointers must stay valid until the sort has run on the stream.
+
     With ``fuse`` and the default kernel configuration the call BLOCKS on
     the current stream once: the truncated sort reads back a flag that
     says whether the full pass sequence must run after all. ``ws``, when
     given, must be sized for the full sequence (as computed below).
     """
     m = load()
-    n = recs.numel() // rec_bytes
+    nbytes = recs if isinstance(recs, int) else recs.numel()
+    n = nbytes // rec_bytes
     if n == 0:
-        return recs
-    dev = recs.device
+        return (recs if isinstance(recs, torch.Tensor)
+                else torch.empty(0, dtype=torch.uint8, device="cuda"))
+    if segments is None:
+        dev = recs.device
+        recs_ptr, seg_t, nsegs, segs = recs.data_ptr(), None, 0, None
+    else:
+        dev = (recs.device if isinstance(recs, torch.Tensor)
+               else out.device if out is not None
+               else torch.device("cuda", torch.cuda.current_device()))
+        recs_ptr, seg_t, nsegs, segs = _segment_table(segments, n,
+                                                      rec_bytes, dev)
+    seg_ptr = seg_t.data_ptr() if seg_t is not None else 0
     if pairs_filled:
         # caller already extracted (e.g. incrementally per fetched chunk,
         # overlapping the fetch phase)
         assert pairs is not None and pairs.numel() >= 2 * n
         prs = pairs[:2 * n]
-    else:
+    elif segments is None:
         prs = extract_pairs(recs, rec_bytes, key_bytes, pairs)
+    else:
+        if pairs is None:
+            pairs = torch.empty(2 * n, dtype=torch.int64, device=dev)
+        assert pairs.numel() >= 2 * n
+        prs = pairs[:2 * n]
+        for first, cnt, ptr in segs:
+            m.extract_pairs(ptr, cnt, rec_bytes, key_bytes,
+                            prs.data_ptr() + 16 * first, _stream(),
+                            idx_base=first)
     if tmp is None:
         tmp = torch.empty_like(prs)
     else:
@@ -270,10 +324,10 @@ def sort_records(recs: torch.Tensor, rec_bytes: int, key_bytes: int = 8,
         assert ws.numel() >= need_ws
     cur, other = prs, tmp
     if out is None:
-        out = torch.empty_like(recs)
+        out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     else:
-        assert out.numel() >= recs.numel()
-        out = out[:recs.numel()]
+        assert out.numel() >= nbytes
+        out = out[:nbytes]
     # truncated sort (kernels.hip sort_records_truncated_u64): LSD over the
     # leading key bits only, tied runs repaired in LDS, full sequence as
     # the fallback for inputs with long runs. -1 = bypassed (fuse off, tie
@@ -281,8 +335,8 @@ def sort_records(recs: torch.Tensor, rec_bytes: int, key_bytes: int = 8,
     # nothing ran, take the full sequence below. Path: last_sort_path().
     if m.sort_records_truncated_u64(
             cur.data_ptr(), other.data_ptr(), n, min(end_bit, 64),
-            key_bytes, ws.data_ptr(), _stream(), recs.data_ptr(),
-            out.data_ptr(), rec_bytes, int(fuse)) != -1:
+            key_bytes, ws.data_ptr(), _stream(), recs_ptr,
+            out.data_ptr(), rec_bytes, int(fuse), seg_ptr, nsegs) != -1:
         return out
     if key_bytes > 8:
         # LSD over the 80-bit key: 16 aux bits first, then the prefix
@@ -298,8 +352,8 @@ def sort_records(recs: torch.Tensor, rec_bytes: int, key_bytes: int = 8,
         # current ablation globals -> fall through to the plain path
         res = m.onesweep_sort_aos_fused_u64(
             cur.data_ptr(), other.data_ptr(), n, 0, min(end_bit, 64),
-            ws.data_ptr(), _stream(), 0, recs.data_ptr(),
-            out.data_ptr(), rec_bytes)
+            ws.data_ptr(), _stream(), 0, recs_ptr,
+            out.data_ptr(), rec_bytes, seg_ptr, nsegs)
         if res != -1:
             return out
     r = m.onesweep_sort_aos_word_u64(cur.data_ptr(), other.data_ptr(), n,
@@ -307,8 +361,9 @@ def sort_records(recs: torch.Tensor, rec_bytes: int, key_bytes: int = 8,
                                      _stream(), 0)
     if r == 1:
         cur, other = other, cur
-    m.gather_records(recs.data_ptr(), cur.data_ptr(), n, rec_bytes, 0,
-                     out.data_ptr(), 0, 0, 0, 0, 0, 0, _stream())
+    m.gather_records(recs_ptr, cur.data_ptr(), n, rec_bytes, 0,
+                     out.data_ptr(), 0, 0, 0, 0, 0, 0, _stream(),
+                     seg_ptr, nsegs)
     return out
 
 

@@ -127,6 +127,78 @@ def coalesce_blocks(blocks: List[BlockRef], max_bytes: int,
     return out
 
 
+class DeviceView:
+    """A zero-copy window on device memory that is not a torch tensor: a
+    run of records a reader left IN PLACE in one of the shuffle's HBM
+    blocks (raw slab memory). ``ptr`` / ``data_ptr()`` is its device
+    address, ``arena_off`` the offset it would have had in the fetch arena
+    (pair indices count from there). Slicing gives a narrower view.
+
+    Valid until the shuffle that owns the block is unregistered."""
+
+    __slots__ = ("ptr", "length", "arena_off")
+
+    def __init__(self, ptr: int, length: int, arena_off: int):
+        self.ptr, self.length, self.arena_off = ptr, length, arena_off
+
+    def __len__(self) -> int:
+        return self.length
+
+    def numel(self) -> int:
+        return self.length
+
+    def data_ptr(self) -> int:
+        return self.ptr
+
+    def __getitem__(self, s: slice) -> "DeviceView":
+        if not isinstance(s, slice):
+            raise TypeError("a DeviceView is sliced, not indexed")
+        a, b, step = s.indices(self.length)
+        if step != 1:
+            raise ValueError("a DeviceView slice is contiguous")
+        return DeviceView(self.ptr + a, max(b - a, 0), self.arena_off + a)
+
+    def __repr__(self) -> str:
+        return (f"DeviceView(ptr={self.ptr:#x}, length={self.length}, "
+                f"arena_off={self.arena_off})")
+
+
+def build_record_segments(ranges, rec_bytes: int,
+                          total_records: Optional[int] = None) -> List[tuple]:
+    """The segment table of a set of record ranges.
+
+    ``ranges``: ``(first_rec, nrec, device_ptr)`` in any order — records
+    ``[first_rec, first_rec + nrec)`` of the virtual arena lie at
+    ``device_ptr``, ``rec_bytes`` apart. Returns the same triples sorted by
+    ``first_rec``, with neighbours that are contiguous in address merged
+    and empty ranges dropped. The ranges must cover ``[0, total)`` exactly
+    once (``total`` = ``total_records``, or wherever they end): a gap or an
+    overlap raises ValueError — a consumer would otherwise gather records
+    from the wrong place."""
+    out: List[tuple] = []
+    pos = 0
+    for first, nrec, ptr in sorted((int(a), int(n), int(p))
+                                   for a, n, p in ranges):
+        if nrec < 0:
+            raise ValueError(f"negative record count at record {first}")
+        if nrec == 0:
+            continue
+        if first > pos:
+            raise ValueError(f"records [{pos}, {first}) are in no segment")
+        if first < pos:
+            raise ValueError(f"records [{first}, {min(pos, first + nrec)}) "
+                             "are in two segments")
+        if out and out[-1][2] + out[-1][1] * rec_bytes == ptr:
+            out[-1] = (out[-1][0], out[-1][1] + nrec, out[-1][2])
+        else:
+            out.append((first, nrec, ptr))
+        pos = first + nrec
+    if total_records is not None and pos != total_records:
+        raise ValueError(f"segments end at record {pos}, expected "
+                         f"{total_records}")
+    return out
+
+
 class FetcherIterator:
     """Async fetch pipeline with byte-budget + per-source flow control."""
 
@@ -134,7 +206,8 @@ class FetcherIterator:
                  start_partition: int, end_partition: int,
                  num_workers: int = 8, seed: Optional[int] = None,
                  arena: Optional[object] = None,
-                 records: Optional[tuple] = None):
+                 records: Optional[tuple] = None,
+                 in_place: bool = False):
         """``records``: optional wide-record spec ``(rec_bytes, key_bytes,
         pairs)``, ``pairs`` an int64 device tensor with two elements per
         record the arena hint can hold. Event-lane fetches whose arena
@@ -142,7 +215,26 @@ class FetcherIterator:
         pair-extract kernel: record ``arena_off // rec_bytes + i`` gets its
         (prefix, aux) pair at that index of ``pairs``. ``pair_ranges()``
         and ``pairs_written()`` say which arena ranges were served that
-        way; every other fetch is a plain copy and the caller extracts."""
+        way; every other fetch is a plain copy and the caller extracts.
+
+        ``in_place=True`` (with ``records``) declares that the consumer
+        takes the records through ``record_segments()`` and not through
+        ``arena``. Under conf ``fusedRecordFetch=inplace`` a fetch that
+        qualifies for the fused lane in ``local`` mode — the block belongs
+        to this executor, a GPU key, whole records, 4-byte aligned — is
+        then NOT copied: only its pairs are extracted, at the indices its
+        (now purely virtual) arena offset gives, and iteration yields a
+        ``DeviceView`` of the block itself instead of an arena slice.
+        Every other fetch is copied into the arena as always. Once any
+        range is in place ``arena`` is None — the buffer has holes — and
+        ``total_bytes`` gives the extent.
+
+        LIFETIME: in-place segments and views point into the shuffle's
+        registered blocks. They are valid until ``unregister_shuffle``;
+        the consumer must have synchronised the GPU work that reads them
+        before it unregisters. Under ``local``/``host``/``off``, or without
+        ``in_place``, nothing is left in place and ``record_segments()``
+        points into the arena only."""
         self.manager = manager
         self.handle = handle
         self.start_partition = start_partition
@@ -173,7 +265,8 @@ class FetcherIterator:
         self._arena_buf = arena            # caller-provided hint (optional)
         self._arena_used = 0
         self._deferred: List[CoalescedFetch] = []  # awaiting arena alloc
-        self.arena = None                  # exact-length view, set when known
+        self._arena_view = None            # exact-length view, set when known
+        self.total_bytes = 0               # arena extent, set with the view
         self.arena_complete = False
         self._inflight_gpu: dict = {}      # event id -> (fetch, t0)
         self._blocking_arena_inflight = 0  # pool fetches writing the arena
@@ -187,6 +280,9 @@ class FetcherIterator:
                            else "off")
         self._pair_starts: List[int] = []  # sorted arena offsets ...
         self._pair_ends: dict = {}         # ... -> end of the fused range
+        # ranges left in place: arena offset -> (device pointer, length)
+        self._in_place = bool(in_place) and records is not None
+        self._inplace_src: dict = {}
         self._pool.submit(self._start_async)
 
     # ------------------------------------------------------------------
@@ -317,7 +413,8 @@ class FetcherIterator:
                     self._arena_used += f.length
                 self._pending.extend(deferred)
         if self.manager.gpu is not None and self._arena_buf is not None:
-            self.arena = self._arena_buf[:self._arena_used]
+            self._arena_view = self._arena_buf[:self._arena_used]
+        self.total_bytes = self._arena_used
         self.arena_complete = True
 
     def _drain_inflight(self) -> None:
@@ -378,7 +475,17 @@ class FetcherIterator:
             # thread polls the event (no blocked thread per fetch)
             try:
                 dst = self._arena_buf.data_ptr() + f.arena_off
-                if self._fused(f, owner):
+                if self._leave_in_place(f, owner):
+                    W, key_bytes, pairs = self._records
+                    idx_base = f.arena_off // W
+                    ev, src = mgr.gpu.issue_extract_records(
+                        f.key, f.addr, f.length, W, key_bytes,
+                        pairs.data_ptr() + 16 * idx_base, idx_base)
+                    with self._lock:
+                        bisect.insort(self._pair_starts, f.arena_off)
+                        self._pair_ends[f.arena_off] = f.arena_off + f.length
+                        self._inplace_src[f.arena_off] = (src, f.length)
+                elif self._fused(f, owner):
                     W, key_bytes, pairs = self._records
                     idx_base = f.arena_off // W
                     ev = mgr.gpu.issue_read_records_into(
@@ -404,7 +511,7 @@ class FetcherIterator:
     def _fused(self, f: CoalescedFetch, owner: int) -> bool:
         """Does this event-lane fetch take the fused record kernel?"""
         mode = self._fuse_mode
-        if mode == "off" or (mode == "local"
+        if mode == "off" or (mode in ("local", "inplace")
                              and owner != self.manager.executor_id):
             return False
         W, _key_bytes, pairs = self._records
@@ -413,6 +520,51 @@ class FetcherIterator:
                 and self._arena_buf.data_ptr() % 4 == 0
                 and pairs.data_ptr() % 16 == 0
                 and 2 * ((f.arena_off + f.length) // W) <= pairs.numel())
+
+    def _leave_in_place(self, f: CoalescedFetch, owner: int) -> bool:
+        """Is this event-lane fetch served where it lies? Exactly the
+        fetches the fused lane takes in ``local`` mode, for a reader that
+        asked for it under conf ``inplace``."""
+        return (self._in_place and self._fuse_mode == "inplace"
+                and owner == self.manager.executor_id
+                and self._fused(f, owner))
+
+    @property
+    def arena(self):
+        """The fetched bytes as one device tensor — None until the extent
+        is known, and None for good once any range was left in place (the
+        buffer then has holes: use ``record_segments()``)."""
+        with self._lock:
+            if self._inplace_src:
+                return None
+        return self._arena_view
+
+    def record_segments(self) -> List[tuple]:
+        """Where the records are, valid once the iterator is drained:
+        ``(first_rec, nrec, device_ptr)`` triples sorted by ``first_rec``
+        that cover every record of the (virtual) arena exactly once,
+        neighbours contiguous in address merged. A range left in place
+        points into its block, everything else into the arena buffer. See
+        the class docstring for how long the pointers stay valid."""
+        if self._records is None:
+            raise RuntimeError("record_segments() needs a record spec")
+        if not self.arena_complete:
+            raise RuntimeError("record_segments() before the fetch finished")
+        W = self._records[0]
+        total = self.total_bytes
+        if total % W:
+            raise ValueError(f"{total} fetched bytes are not whole "
+                             f"{W}-byte records")
+        with self._lock:
+            placed = sorted(self._inplace_src.items())
+        base = self._arena_buf.data_ptr() if self._arena_buf is not None else 0
+        ranges, pos = [], 0
+        for off, (src, length) in placed + [(total, (0, 0))]:
+            if off > pos:     # copied bytes between two in-place ranges
+                ranges.append((pos // W, (off - pos) // W, base + pos))
+            ranges.append((off // W, length // W, src))
+            pos = off + length
+        return build_record_segments(ranges, W, total // W)
 
     def pair_ranges(self) -> List[tuple]:
         """Arena ranges ``(offset, length)`` whose pairs the fused lane
@@ -465,7 +617,13 @@ class FetcherIterator:
                 if err is not None:
                     self._results.put(FetchResult(f, None, error=err))
                 else:
-                    data = self._arena_buf[f.arena_off:f.arena_off + f.length]
+                    with self._lock:
+                        placed = self._inplace_src.get(f.arena_off)
+                    if placed is not None:   # never a copy: the block itself
+                        data = DeviceView(placed[0], f.length, f.arena_off)
+                    else:
+                        data = self._arena_buf[f.arena_off:
+                                               f.arena_off + f.length]
                     self._results.put(FetchResult(
                         f, data,
                         latency_ms=(time.perf_counter() - t0) * 1e3))
@@ -522,8 +680,14 @@ class FetcherIterator:
         try:
             while True:
                 with self._lock:
-                    if self._outstanding == 0 and self._hop2_pending == 0:
-                        break
+                    drained = (self._outstanding == 0
+                               and self._hop2_pending == 0)
+                # an error of hop 1 / hop 2 is queued BEFORE its task counts
+                # itself done: whatever is still queued is looked at, so a
+                # failure that lost the race to this check still fails the
+                # task instead of ending it as if it were empty
+                if drained and self._results.empty():
+                    break
                 t0 = time.perf_counter_ns()
                 res = self._results.get()
                 self.metrics.fetch_wait_ns += time.perf_counter_ns() - t0
@@ -582,14 +746,15 @@ class ShuffleReader:
 
     def __init__(self, manager: ShuffleManager, handle: ShuffleHandle,
                  start_partition: int, end_partition: int, arena=None,
-                 records=None):
+                 records=None, in_place: bool = False):
         self.manager = manager
         self.handle = handle
         self.start_partition = start_partition
         self.end_partition = end_partition
         self.fetcher = FetcherIterator(manager, handle,
                                        start_partition, end_partition,
-                                       arena=arena, records=records)
+                                       arena=arena, records=records,
+                                       in_place=in_place)
 
     def __iter__(self):
         return iter(self.fetcher)

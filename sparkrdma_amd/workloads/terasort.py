@@ -238,13 +238,18 @@ class TeraSort:
         if self.wide:
             # record spec: local one-sided fetches run as the fused copy +
             # pair-extract kernel and fill each chunk's pair buffer as the
-            # records land (the chunks fetch concurrently: one buffer each)
+            # records land (the chunks fetch concurrently: one buffer each).
+            # in_place: blocks this executor owns are not copied at all
+            # (conf fusedRecordFetch=inplace) — the sort below gathers the
+            # records from wherever reader.record_segments() says they
+            # are, which is why unregister_shuffle comes after it
             Wb = self.RECORD_BYTES
             pair_bufs = [self._sort_tmp(2 * (ar.numel() // Wb) + 16,
                                         self._pairs_attr(h))
                          for h, ar in enumerate(arenas)]
             readers = [eng.manager.get_reader(handle, a, b, arena=ar,
-                                              records=(Wb, 10, pb))
+                                              records=(Wb, 10, pb),
+                                              in_place=True)
                        for (a, b), ar, pb in zip(spans, arenas, pair_bufs)]
         else:
             readers = [eng.manager.get_reader(handle, a, b, arena=ar)
@@ -271,23 +276,30 @@ class TeraSort:
                 parts = reader.collect_partitions()
             ts_ = time.perf_counter()
             arena = getattr(reader.fetcher, "arena", None)
-            if self.device == "cuda" and arena is not None:
-                self._check_chunk_fits(arena.numel(), h)
-            if self.wide and arena is not None:
+            if self.wide and eng.manager.gpu is not None:
+                # the records are where the reader left them: in the arena
+                # buffer and/or in place in this executor's blocks (then
+                # there is no arena tensor); one code path for both
                 import torch
                 from ..ops.radix import sort_records
-                nrec = arena.numel() // self.RECORD_BYTES
+                total = reader.fetcher.total_bytes
+                self._check_chunk_fits(total, h)
+                nrec = total // self.RECORD_BYTES
                 out = sort_records(
-                    arena, self.RECORD_BYTES, key_bytes=10,
+                    total, self.RECORD_BYTES, key_bytes=10,
                     end_bit=64 - chunk_shared_bits,
-                    out=self._rec_out(arena.numel()),
+                    out=self._rec_out(total),
                     pairs=self._sort_tmp(2 * nrec, self._pairs_attr(h)),
                     tmp=self._sort_tmp(2 * nrec, "_tmp_cache"),
                     ws=self._sort_ws(),
-                    pairs_filled=pre_extracted)
+                    pairs_filled=pre_extracted,
+                    segments=reader.fetcher.record_segments())
+                # the in-place segments die with unregister_shuffle below:
+                # everything that reads them has run once this returns
                 torch.cuda.synchronize()
                 outs.append(out)
             elif self.device == "cuda" and arena is not None:
+                self._check_chunk_fits(arena.numel(), h)
                 # fetches landed pre-placed in one device buffer: sort it
                 # directly (no concat pass); tmp/ws persist across steps
                 # so a 40 GB step performs no large allocations at all
@@ -354,7 +366,9 @@ class TeraSort:
 
     def _extract_while_fetching(self, reader,
                                 pairs_attr: str = "_pairs_cache") -> bool:
-        """Iterate the fetcher. Blocks whose fetch ran as the fused kernel
+        """Iterate the fetcher. Blocks whose fetch ran as the fused kernel,
+        or was left in place (then the view is a DeviceView of the block,
+        placed by its virtual arena offset),
         already have their pairs; for every other CONTIGUOUS landed run
         the (prefix, aux) pair extraction is launched here — it overlaps
         the in-flight fetches instead of re-reading the full arena
@@ -363,6 +377,7 @@ class TeraSort:
         pass — growth/non-tensor fallback)."""
         import torch
         from ..ops import load
+        from ..reader import DeviceView
         hs = load()
         W = self.RECORD_BYTES
         f = reader.fetcher
@@ -392,11 +407,16 @@ class TeraSort:
             covered += run_len
 
         for _ref, view in f:
-            if (not isinstance(view, torch.Tensor)
+            if isinstance(view, DeviceView):
+                # left in place: it lies outside the arena buffer, its
+                # VIRTUAL offset says which pairs are its own
+                boff = view.arena_off
+            elif (not isinstance(view, torch.Tensor)
                     or f._arena_buf is not buf):
                 ok = False       # grew / non-arena chunk: full re-extract
                 continue
-            boff = view.data_ptr() - base
+            else:
+                boff = view.data_ptr() - base
             nb = view.numel()
             if not (0 <= boff and boff + nb <= cap):
                 ok = False
@@ -410,9 +430,7 @@ class TeraSort:
                 flush()
                 run_off, run_len = boff, nb
         flush()
-        arena = f.arena
-        return bool(ok and arena is not None
-                    and covered == arena.numel())
+        return bool(ok and f.arena_complete and covered == f.total_bytes)
 
     def _sort_tmp(self, n_i64: int, attr: str = "_tmp_cache"):
         import torch
