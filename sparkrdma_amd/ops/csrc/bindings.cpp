@@ -119,13 +119,7 @@ PYBIND11_MODULE(_hipshuffle, m) {
         py::arg("lo_idx"), py::arg("offsets"), py::arg("out_key"),
         py::arg("out_a"), py::arg("out_b"), py::arg("stream") = 0);
   m.def("onesweep_workspace_bytes", &hs::onesweep_workspace_bytes);
-  m.def("set_aos_tile", &hs::set_aos_tile);
-  m.def("set_pass_stage", &hs::set_pass_stage);
   m.def("set_timing_buf", &hs::set_timing_buf);
-  m.def("set_sort_mode", &hs::set_sort_mode);
-  m.def("set_lookback_mode", &hs::set_lookback_mode);
-  m.def("set_split_exchange", &hs::set_split_exchange);
-  m.def("set_lean_pass", &hs::set_lean_pass);
   m.def("set_tie_repair", &hs::set_tie_repair);
   m.def("last_sort_path", &hs::last_sort_path);
   m.def("tie_repair_tile", &hs::tie_repair_tile);
@@ -143,10 +137,6 @@ PYBIND11_MODULE(_hipshuffle, m) {
         py::arg("stream"), py::arg("recs"), py::arg("out"),
         py::arg("rec_bytes"), py::arg("fuse") = 1, py::arg("segs") = 0,
         py::arg("nsegs") = 0, py::call_guard<py::gil_scoped_release>());
-  m.def("onesweep_sort_aos7_u64", &hs::onesweep_sort_aos7_u64,
-        py::arg("pairs"), py::arg("tmp_pairs"), py::arg("n"),
-        py::arg("start_bit"), py::arg("end_bit"), py::arg("ws"),
-        py::arg("stream") = 0, py::call_guard<py::gil_scoped_release>());
   m.def("onesweep_sort_aos_u64", &hs::onesweep_sort_aos_u64,
         py::arg("pairs"), py::arg("tmp_pairs"), py::arg("n"),
         py::arg("start_bit"), py::arg("end_bit"), py::arg("ws"),

@@ -98,16 +98,7 @@ void join_emit(uintptr_t a_keys, uintptr_t a_vals, uint32_t na,
                uintptr_t offsets, uintptr_t out_key, uintptr_t out_a,
                uintptr_t out_b, uintptr_t stream);
 size_t onesweep_workspace_bytes(uint32_t n, int passes);
-void set_aos_tile(int t);
-void set_pass_stage(int s);
 void set_timing_buf(uintptr_t p);
-void set_sort_mode(int m);
-void set_lookback_mode(int m);
-void set_split_exchange(int m);
-void set_lean_pass(int m);
-int onesweep_sort_aos7_u64(uintptr_t pairs, uintptr_t tmp_pairs, uint32_t n,
-                           int start_bit, int end_bit, uintptr_t ws,
-                           uintptr_t stream);
 int onesweep_sort_aos_u64(uintptr_t pairs, uintptr_t tmp_pairs, uint32_t n,
                           int start_bit, int end_bit, uintptr_t ws,
                           uintptr_t stream);

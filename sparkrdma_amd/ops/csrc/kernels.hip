@@ -565,35 +565,6 @@ __device__ __forceinline__ void lookback_walk(
   pref[tid] = (uint32_t)run;
 }
 
-// TRANSPOSED-descriptor walk: desc laid out [ND][nb] so digit `tid`'s
-// predecessors are CONTIGUOUS backwards — 16 descriptors share one
-// 128-B line, so a completed prefix region costs nb/16 line fills
-// instead of nb (the r01 [nb][ND] layout made every probe its own
-// line). Publish is a scattered 8-B store per digit (one line each) —
-// worth it when walks span many predecessors (512-block resident
-// windows at 64M records).
-template <int ND>
-__device__ __forceinline__ void lookback_walk_t(
-    uint64_t* __restrict__ desc, uint32_t nb, uint32_t b, int tid,
-    uint64_t my_total, uint32_t* __restrict__ pref) {
-  uint64_t* row = desc + (uint64_t)tid * nb;
-  uint64_t run = 0;
-  for (int64_t j = (int64_t)b - 1; j >= 0;) {
-    uint64_t v = __hip_atomic_load(&row[j], __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-    if ((v & FLAG_MASK) == 0) {
-      __builtin_amdgcn_s_sleep(2);
-      continue;
-    }
-    run += v & VAL_MASK;
-    if ((v & FLAG_MASK) == FLAG_INC) break;
-    --j;
-  }
-  __hip_atomic_store(&row[b], FLAG_INC | (run + my_total),
-                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  pref[tid] = (uint32_t)run;
-}
-
 // Global digit totals of EVERY pass in one read (digit counts are
 // order-independent, so pass k's totals can be computed from pass 0's
 // input).
@@ -628,49 +599,44 @@ __global__ __launch_bounds__(BLOCK) void onesweep_hist_all_kernel(
   }
 }
 
-// AOS=true: elements are interleaved (key, val) 16-byte records — one
+// One LSD pass over an 8-bit digit: each block ranks a tile of BS * IT
+// elements, publishes its digit counts, reorders the tile by digit in
+// LDS, and writes every digit run to its place in the output, found
+// from the per-digit bases in key_dst / val_dst and the lookback prefix.
+// AOS = false: keys and vals are separate u64 arrays; the keys go
+// through the LDS exchange first, the vals (HAS_VAL) after them.
+// AOS = true: elements are interleaved (key, val) 16-byte records — one
 // dwordx4 load per element, a pair LDS exchange, ONE 16-byte store per
 // element, and 2x-longer digit write bursts (measured: scattered-write
-// bandwidth doubles from 128 B to 256 B bursts — profiles/).
-// LEAN (AoS only): phase A loads ONLY the sort word and the exchange
-// RE-READS the full pair from global (L2-hot: the tile was just pulled)
-// — drops the val_reg/key_reg liveness so VGPRs fit 6 waves/SIMD =
-// 3 blocks/CU resident, hiding more of the lookback wait while keeping
-// full-tile burst lengths (the 2048-tile route paid burst halving +
-// 2x descriptors for its occupancy; this pays only L1/L2 re-reads).
-template <bool HAS_VAL, int IT, bool AOS, int BS = BLOCK, int PBITS = 8,
-          bool LEAN = false, bool FUSE_GATHER = false>
-__global__ __launch_bounds__(BS)
-__attribute__((amdgpu_waves_per_eu(LEAN ? 6 : 1))) void onesweep_pass_kernel(
+// bandwidth doubles from 128 B to 256 B bursts — profiles/). sort_word
+// selects which u64 of the pair carries the digit.
+// FUSE_GATHER (AoS only): the writeout copies each pair's whole RECORD
+// instead of the pair — the final sort pass IS the gather.
+// timing, when set, accumulates the AoS phases' clock ticks.
+template <bool HAS_VAL, int IT, bool AOS, int BS = BLOCK,
+          bool FUSE_GATHER = false>
+__global__ __launch_bounds__(BS) void onesweep_pass_kernel(
     const uint64_t* __restrict__ keys, const uint64_t* __restrict__ vals,
     uint32_t n, int shift, uint64_t* __restrict__ desc /* [nb][ND] */,
     uint32_t* __restrict__ ticket,
     const uint64_t* __restrict__ key_dst, const uint64_t* __restrict__ val_dst,
-    int stage = 3, uint64_t* __restrict__ timing = nullptr,
-    const uint32_t* __restrict__ hist_pref = nullptr, int sort_word = 0,
-    int lb_mode = 0 /* 0: [nb][ND] descriptors, 1: transposed [ND][nb] */,
-    int split_exch = 0, /* AoS: exchange+writeout in N sub-tile rounds
-                           (0/1 = single round); the LDS exchange buffer
-                           shrinks by N so more blocks stay resident to
-                           hide the lookback wait */
+    uint64_t* __restrict__ timing = nullptr, int sort_word = 0,
     const uint32_t* __restrict__ rec_words = nullptr, /* FUSE_GATHER */
     uint32_t rec_w4 = 0 /* record words; key_dst then holds per-digit
-                           RECORD base addresses and the writeout copies
-                           whole records instead of pairs — the final
-                           sort pass IS the gather */,
+                           RECORD base addresses */,
     const RecSegment* __restrict__ rec_segs = nullptr, /* FUSE_GATHER: */
     uint32_t rec_nsegs = 0 /* record sources (record_src); 0 = contiguous
                               from rec_words */) {
+  constexpr int PBITS = 8;
   constexpr int ND = 1 << PBITS;
   extern __shared__ char smem_raw[];
   constexpr int TILE_T = BS * IT;
   constexpr int NWT = BS / kWave;
   using u64x2 = __attribute__((ext_vector_type(2))) unsigned long long;
-  const int ecap = (AOS && split_exch > 1) ? TILE_T / split_exch : TILE_T;
-  uint64_t* exch = reinterpret_cast<uint64_t*>(smem_raw);  // [ecap] or
-  u64x2* exch2 = reinterpret_cast<u64x2*>(smem_raw);       // [ecap] pairs
+  uint64_t* exch = reinterpret_cast<uint64_t*>(smem_raw);  // [TILE_T] or
+  u64x2* exch2 = reinterpret_cast<u64x2*>(smem_raw);       // [TILE_T] pairs
   uint32_t* counters = reinterpret_cast<uint32_t*>(
-      exch + (AOS ? 2 * ecap : TILE_T));
+      exch + (AOS ? 2 * TILE_T : TILE_T));
   uint32_t* start = counters + NWT * ND;
   uint32_t* pref = start + ND;
   uint32_t* sums = pref + ND;  // [BS]
@@ -680,8 +646,7 @@ __attribute__((amdgpu_waves_per_eu(LEAN ? 6 : 1))) void onesweep_pass_kernel(
   const int tid = threadIdx.x;
   const int lane = tid & (kWave - 1);
   const int wave = tid >> 6;
-  if (tid == 0)
-    *vb_sh = hist_pref ? blockIdx.x : atomicAdd(ticket, 1);
+  if (tid == 0) *vb_sh = atomicAdd(ticket, 1);
   for (int d = tid; d < NWT * ND; d += BS) counters[d] = 0;
   __syncthreads();
   const uint32_t b = *vb_sh;  // execution-ordered virtual block id
@@ -696,54 +661,29 @@ __attribute__((amdgpu_waves_per_eu(LEAN ? 6 : 1))) void onesweep_pass_kernel(
   // flight before the serial per-wave LDS counter chain starts — fusing
   // load+rank serialized loads behind LDS RMWs (phase A 11.4 -> 8.2 us
   // per block, full sort 7.56 -> 7.15 ms / 64M).
-  uint64_t key_reg[(AOS && LEAN) ? 1 : IT];
-  uint64_t val_reg[(AOS && !LEAN) ? IT : 1];
+  uint64_t key_reg[IT];
+  uint64_t val_reg[AOS ? IT : 1];
   uint32_t digrank[IT];
   const uint64_t chunk = tile_start + (uint64_t)wave * (IT * kWave);
-  if (!(AOS && LEAN)) {
 #pragma unroll
-    for (int i = 0; i < IT; ++i) {
-      uint64_t e = chunk + (uint64_t)i * kWave + lane;
-      bool valid = e < n;
-      if (AOS) {
-        u64x2 kv = valid ? reinterpret_cast<const u64x2*>(keys)[e]
-                         : u64x2{0, 0};
-        key_reg[i] = kv.x;
-        val_reg[(AOS && !LEAN) ? i : 0] = kv.y;
-      } else {
-        key_reg[i] = valid ? keys[e] : 0;
-      }
+  for (int i = 0; i < IT; ++i) {
+    uint64_t e = chunk + (uint64_t)i * kWave + lane;
+    bool valid = e < n;
+    if (AOS) {
+      u64x2 kv = valid ? reinterpret_cast<const u64x2*>(keys)[e]
+                       : u64x2{0, 0};
+      key_reg[i] = kv.x;
+      val_reg[AOS ? i : 0] = kv.y;
+    } else {
+      key_reg[i] = valid ? keys[e] : 0;
     }
   }
   // rank in iteration PAIRS: both iterations' per-bit ballots are held
   // in registers, so the pair's ranks and the single LDS counter update
   // per digit need only ONE serial LDS round trip per two iterations —
-  // the serial chain was 13% of a pass (stage-9 ablation).
+  // the serial chain was 13% of a pass.
   static_assert(IT % 2 == 0, "pair ranking needs even IT");
   const uint64_t lt = (1ull << lane) - 1;
-  if (AOS && LEAN) {
-    // single-iteration ranking: one ballot set live at a time — the
-    // VGPR budget (not LDS) is what buys the 3rd resident block per CU;
-    // the serial LDS chain it re-lengthens is hidden by that occupancy
-    const int sw = sort_word ? 1 : 0;
-#pragma unroll
-    for (int i = 0; i < IT; ++i) {
-      uint64_t e = chunk + (uint64_t)i * kWave + lane;
-      bool valid = e < n;
-      uint64_t k = valid ? keys[2 * e + sw] : 0;
-      uint32_t d = (uint32_t)(k >> shift) & (ND - 1);
-      uint64_t vm = __ballot(valid);
-      uint32_t r = 0;
-      if (valid) {
-        uint64_t match = match_lanes<PBITS>(d, vm);
-        uint32_t rank_in_iter = (uint32_t)__popcll(match & lt);
-        uint32_t base = my[d];
-        r = base + rank_in_iter;
-        if (rank_in_iter == 0) my[d] = base + (uint32_t)__popcll(match);
-      }
-      digrank[i] = (d << 16) | (valid ? r : 0);
-    }
-  } else
 #pragma unroll
   for (int c = 0; c < IT / 2; ++c) {
     const int i0 = 2 * c, i1 = 2 * c + 1;
@@ -751,21 +691,9 @@ __attribute__((amdgpu_waves_per_eu(LEAN ? 6 : 1))) void onesweep_pass_kernel(
     uint64_t e1 = chunk + (uint64_t)i1 * kWave + lane;
     bool val0 = e0 < n, val1 = e1 < n;
     // sort_word selects WHICH u64 of the AoS pair orders this pass
-    // (the 80-bit-key path sorts 16 aux bits before the 64 prefix bits).
-    // LEAN keeps NO register arrays: the sort word loads here and the
-    // exchange re-reads the pair from the L2-hot tile — the VGPR budget
-    // is what buys the 3rd resident block per CU.
-    uint64_t sk0, sk1;
-    if (AOS && LEAN) {
-      const int sw = sort_word ? 1 : 0;
-      sk0 = val0 ? keys[2 * e0 + sw] : 0;
-      sk1 = val1 ? keys[2 * e1 + sw] : 0;
-    } else {
-      sk0 = (AOS && !LEAN && sort_word)
-          ? val_reg[(AOS && !LEAN) ? i0 : 0] : key_reg[(AOS && LEAN) ? 0 : i0];
-      sk1 = (AOS && !LEAN && sort_word)
-          ? val_reg[(AOS && !LEAN) ? i1 : 0] : key_reg[(AOS && LEAN) ? 0 : i1];
-    }
+    // (the 80-bit-key path sorts 16 aux bits before the 64 prefix bits)
+    uint64_t sk0 = (AOS && sort_word) ? val_reg[AOS ? i0 : 0] : key_reg[i0];
+    uint64_t sk1 = (AOS && sort_word) ? val_reg[AOS ? i1 : 0] : key_reg[i1];
     uint32_t d0 = (uint32_t)(sk0 >> shift) & (ND - 1);
     uint32_t d1 = (uint32_t)(sk1 >> shift) & (ND - 1);
     uint64_t vm0 = __ballot(val0), vm1 = __ballot(val1);
@@ -775,8 +703,8 @@ __attribute__((amdgpu_waves_per_eu(LEAN ? 6 : 1))) void onesweep_pass_kernel(
 #pragma unroll
     for (int b = 0; b < PBITS; ++b) v1[b] = __ballot((d1 >> b) & 1);
     // per-chunk bases read BEFORE this chunk's single update round
-    uint32_t base0 = (val0 && stage != 9) ? my[d0] : 0;
-    uint32_t base1 = (val1 && stage != 9) ? my[d1] : 0;
+    uint32_t base0 = val0 ? my[d0] : 0;
+    uint32_t base1 = val1 ? my[d1] : 0;
     uint64_t m0 = match_votes<PBITS>(v0, vm0, d0);
     uint64_t m1 = match_votes<PBITS>(v1, vm1, d1);
     uint64_t cross1 = match_votes<PBITS>(v0, vm0, d1);  // i0 elems == d1
@@ -785,17 +713,15 @@ __attribute__((amdgpu_waves_per_eu(LEAN ? 6 : 1))) void onesweep_pass_kernel(
                   + (uint32_t)__popcll(m1 & lt);
     digrank[i0] = (d0 << 16) | (val0 ? r0 : 0);
     digrank[i1] = (d1 << 16) | (val1 ? r1 : 0);
-    if (stage != 9) {
-      // one LDS update per digit per PAIR: the i0 leader of a digit adds
-      // both iterations' counts; digits present only in i1 are added by
-      // their i1 leader
-      if (val0 && (m0 & lt) == 0) {
-        uint64_t cross0 = match_votes<PBITS>(v1, vm1, d0);
-        my[d0] = base0 + (uint32_t)__popcll(m0) + (uint32_t)__popcll(cross0);
-      }
-      if (val1 && (m1 & lt) == 0 && cross1 == 0)
-        my[d1] = base1 + (uint32_t)__popcll(m1);
+    // one LDS update per digit per PAIR: the i0 leader of a digit adds
+    // both iterations' counts; digits present only in i1 are added by
+    // their i1 leader
+    if (val0 && (m0 & lt) == 0) {
+      uint64_t cross0 = match_votes<PBITS>(v1, vm1, d0);
+      my[d0] = base0 + (uint32_t)__popcll(m0) + (uint32_t)__popcll(cross0);
     }
+    if (val1 && (m1 & lt) == 0 && cross1 == 0)
+      my[d1] = base1 + (uint32_t)__popcll(m1);
   }
   __syncthreads();
 
@@ -817,16 +743,10 @@ __attribute__((amdgpu_waves_per_eu(LEAN ? 6 : 1))) void onesweep_pass_kernel(
   // LDS exchange below (the walk is wait-dominated: it costs ~30% of the
   // pass when run serially here — profiles/r01)
   uint64_t my_total = 0;
-  if (hist_pref) {
-    // no-lookback mode: cross-block prefixes were precomputed by the
-    // hist+scan pre-pass (kills the ~10us/block lookback wait)
-    if (tid < ND) pref[tid] = hist_pref[(uint64_t)b * ND + tid];
-  } else if (tid < ND) {
+  if (tid < ND) {
     my_total = start[tid];
-    uint64_t* slot = lb_mode
-        ? &desc[(uint64_t)tid * gridDim.x + b]
-        : &desc[(uint64_t)b * ND + tid];
-    if (stage == 0 || b == 0) {  // stage 0: ablation, WRONG results
+    uint64_t* slot = &desc[(uint64_t)b * ND + tid];
+    if (b == 0) {
       __hip_atomic_store(slot, FLAG_INC | my_total, __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_AGENT);
       pref[tid] = 0;
@@ -840,79 +760,54 @@ __attribute__((amdgpu_waves_per_eu(LEAN ? 6 : 1))) void onesweep_pass_kernel(
 
   uint64_t t1 = timing ? __builtin_amdgcn_s_memrealtime() : 0;
   if (AOS) {
-    uint64_t t2 = t1, t3 = t1;
-    const uint32_t off_mask = stage < 3 ? 1023u : 0xFFFFFFFFu;
-    const int rounds = split_exch > 1 ? split_exch : 1;
-    for (int round = 0; round < rounds; ++round) {
-      if (round) __syncthreads();     // previous half's writeout done
-      if (stage >= 2) {
-        // pair exchange first: the deferred lookback's wait overlaps it
+    // pair exchange first: the deferred lookback's wait overlaps it
 #pragma unroll
-        for (int i = 0; i < IT; ++i) {
-          uint64_t e = chunk + (uint64_t)i * kWave + lane;
-          if (e < n) {
-            uint32_t d = digrank[i] >> 16;
-            uint32_t j = start[d] + my[d] + (digrank[i] & 0xFFFF);
-            uint32_t jl = j - (uint32_t)(round * ecap);
-            if (jl < (uint32_t)ecap) {
-              if (LEAN)
-                exch2[jl] = reinterpret_cast<const u64x2*>(keys)[e];
-              else
-                exch2[jl] = u64x2{key_reg[i],
-                                  val_reg[(AOS && !LEAN) ? i : 0]};
-            }
-          }
-        }
+    for (int i = 0; i < IT; ++i) {
+      uint64_t e = chunk + (uint64_t)i * kWave + lane;
+      if (e < n) {
+        uint32_t d = digrank[i] >> 16;
+        uint32_t j = start[d] + my[d] + (digrank[i] & 0xFFFF);
+        exch2[j] = u64x2{key_reg[i], val_reg[AOS ? i : 0]};
       }
-      if (round == 0) {
-        t2 = timing ? __builtin_amdgcn_s_memrealtime() : 0;
-        if (!hist_pref && stage != 0 && b != 0 && tid < ND) {
-          if (lb_mode)
-            lookback_walk_t<ND>(desc, gridDim.x, b, tid, my_total, pref);
-          else
-            lookback_walk<ND>(desc, b, tid, my_total, pref);
-        }
-        if (stage < 2 && !timing) return;  // ablation
+    }
+    uint64_t t2 = timing ? __builtin_amdgcn_s_memrealtime() : 0;
+    if (b != 0 && tid < ND) lookback_walk<ND>(desc, b, tid, my_total, pref);
+    __syncthreads();
+    uint64_t t3 = timing ? __builtin_amdgcn_s_memrealtime() : 0;
+    if (FUSE_GATHER) {
+      // copy each slot's RECORD to its final position: key_dst[d]
+      // holds per-digit record bases. Each slot's pair is replaced IN
+      // PLACE by its (record source, destination) addresses — digit,
+      // offset and index derived once per slot — then the block runs
+      // the same batched word copy as gather_records (writes coalesce
+      // within digit runs, reads are the random per-record chunks the
+      // separate gather paid anyway). Block-uniform code: every thread
+      // reaches the barrier.
+      GatherSlot* slots = reinterpret_cast<GatherSlot*>(smem_raw);
+      for (uint32_t j = tid; j < tile_n; j += BS) {
+        u64x2 kv = exch2[j];
+        uint32_t d = (uint32_t)((uint64_t)(sort_word ? kv.y : kv.x)
+                                >> shift) & (ND - 1);
+        uint32_t off = pref[d] + (j - start[d]);
+        uint64_t idx = (uint64_t)kv.y & AUX_IDX_MASK;
+        slots[j] = GatherSlot{
+            record_src(rec_words, rec_segs, rec_nsegs, idx, rec_w4),
+            reinterpret_cast<uint32_t*>(key_dst[d]) +
+                (uint64_t)off * rec_w4};
       }
       __syncthreads();
-      if (round == 0) t3 = timing ? __builtin_amdgcn_s_memrealtime() : 0;
-      if (FUSE_GATHER) {
-        // copy each slot's RECORD to its final position: key_dst[d]
-        // holds per-digit record bases. Each slot's pair is replaced IN
-        // PLACE by its (record source, destination) addresses — digit,
-        // offset and index derived once per slot — then the block runs
-        // the same batched word copy as gather_records (writes coalesce
-        // within digit runs, reads are the random per-record chunks the
-        // separate gather paid anyway). Block-uniform code: FUSE_GATHER
-        // runs a single round and every thread reaches the barrier.
-        GatherSlot* slots = reinterpret_cast<GatherSlot*>(smem_raw);
-        for (uint32_t j = tid; j < tile_n; j += BS) {
+      copy_record_words<BS, GATHER_BATCH>(slots, tile_n, rec_w4);
+    } else {
+#pragma unroll
+      for (int i = 0; i < IT; ++i) {
+        uint32_t j = (uint32_t)i * BS + tid;
+        if (j < tile_n) {
           u64x2 kv = exch2[j];
           uint32_t d = (uint32_t)((uint64_t)(sort_word ? kv.y : kv.x)
                                   >> shift) & (ND - 1);
-          uint32_t off = (pref[d] + (j - start[d])) & off_mask;
-          uint64_t idx = (uint64_t)kv.y & AUX_IDX_MASK;
-          slots[j] = GatherSlot{
-              record_src(rec_words, rec_segs, rec_nsegs, idx, rec_w4),
-              reinterpret_cast<uint32_t*>(key_dst[d]) +
-                  (uint64_t)off * rec_w4};
-        }
-        __syncthreads();
-        copy_record_words<BS, GATHER_BATCH>(slots, tile_n, rec_w4);
-      } else {
-#pragma unroll
-      for (int i = 0; i < IT; ++i) {
-        uint32_t jl = (uint32_t)i * BS + tid;
-        if (jl >= (uint32_t)ecap) break;
-        uint32_t j = (uint32_t)round * ecap + jl;
-        if (j < tile_n) {
-          u64x2 kv = exch2[jl];
-          uint32_t d = (uint32_t)((uint64_t)(sort_word ? kv.y : kv.x)
-                                  >> shift) & (ND - 1);
-          uint32_t off = (pref[d] + (j - start[d])) & off_mask;
+          uint32_t off = pref[d] + (j - start[d]);
           reinterpret_cast<u64x2*>(key_dst[d])[off] = kv;
         }
-      }
       }
     }
     if (timing && tid == 0) {
@@ -920,16 +815,11 @@ __attribute__((amdgpu_waves_per_eu(LEAN ? 6 : 1))) void onesweep_pass_kernel(
       atomicAdd(&timing[0], t1 - t0);  // phase A (+scans+publish)
       atomicAdd(&timing[1], t2 - t1);  // exchange
       atomicAdd(&timing[2], t3 - t2);  // lookback walk + barrier
-      atomicAdd(&timing[3], t4 - t3);  // writeout (+2nd round when split)
+      atomicAdd(&timing[3], t4 - t3);  // writeout
     }
     return;
   }
-  if (!hist_pref && b != 0 && tid < ND) {
-    if (lb_mode)
-      lookback_walk_t<ND>(desc, gridDim.x, b, tid, my_total, pref);
-    else
-      lookback_walk<ND>(desc, b, tid, my_total, pref);
-  }
+  if (b != 0 && tid < ND) lookback_walk<ND>(desc, b, tid, my_total, pref);
 
   // SoA path: key exchange + write-out, then val exchange + write-out
 #pragma unroll
@@ -1714,43 +1604,24 @@ size_t sort_workspace_bytes(uint32_t n) {
 // Onesweep sort: ws layout = totals u32[passes*256] | key_dst u64[256] |
 // val_dst u64[256] | ticket u32 (+pad) | desc u32[nb*256].
 constexpr int OS_ITEMS = 16;  // SoA: 4096-elem tiles @ 256 threads
-// AoS tile selected at runtime: 4096 (512thr x IT8, 2 blocks/CU) or
-// 8192 (512thr x IT16, 1 block/CU, 512B write bursts)
-static int g_aos_tile = 4096;
-void set_aos_tile(int t) { g_aos_tile = t; }
-// ablation: 1 = rank+lookback only, 2 = full work but stores land in a
-// compact dummy window (isolates scattered-store cost), 3 = normal
-static int g_pass_stage = 3;
-void set_pass_stage(int s) { g_pass_stage = s; }
-// sort cross-block-prefix mode: 0 = decoupled lookback (one kernel per
-// pass; measured fastest: 6.2 vs 7.0 ms for the hist+scan pre-pass at
-// 64M — the pre-pass re-read outweighs the lookback wait), 1 = hist+scan
-static int g_sort_mode = 0;
-void set_sort_mode(int m) { g_sort_mode = m; }
+constexpr int OS_AOS_BS = 512;  // AoS: 4096-elem tiles @ 512 threads,
+constexpr int OS_AOS_ITEMS = 8;  // 2 blocks/CU resident
+constexpr int OS_TILE = BLOCK * OS_ITEMS;
+static_assert(OS_AOS_BS * OS_AOS_ITEMS == OS_TILE, "one tile size");
 // optional phase-timing accumulator: u64[4] = {phaseA, exch, lookback, writeout}
 static uint64_t* g_timing_buf = nullptr;
 void set_timing_buf(uintptr_t p) { g_timing_buf = reinterpret_cast<uint64_t*>(p); }
-// descriptor layout: 0 = [nb][ND] (r01), 1 = transposed [ND][nb] (walk
-// reads contiguous backwards — 16 descriptors/line)
-static int g_lb_mode = 0;
-void set_lookback_mode(int m) { g_lb_mode = m; }
-// AoS split exchange: halve the LDS exchange buffer (2 rounds) so 3
-// blocks/CU stay resident and hide more of the lookback wait
-static int g_split_exch = 0;
-void set_split_exchange(int m) { g_split_exch = m; }
-// AoS register-lean variant (re-reads pairs at exchange): 3 blocks/CU
-static int g_lean = 0;
-void set_lean_pass(int m) { g_lean = m; }
 
 static inline uint32_t os_num_tiles_t(uint32_t n, int tile) {
   return (uint32_t)(((uint64_t)n + tile - 1) / tile);
 }
 static inline uint32_t os_num_tiles(uint32_t n) {
-  return os_num_tiles_t(n, BLOCK * OS_ITEMS);
+  return os_num_tiles_t(n, OS_TILE);
 }
 
 size_t onesweep_workspace_bytes(uint32_t n, int passes) {
-  uint32_t nb = os_num_tiles_t(n, 4096);  // smallest tile = max desc size
+  // SoA and AoS passes both run OS_TILE-element tiles: the size is exact
+  uint32_t nb = os_num_tiles(n);
   return (size_t)passes * 256 * 4 + 256 * 8 * 2 + 16 +
          (size_t)nb * 256 * 8;
 }
@@ -1758,79 +1629,61 @@ size_t onesweep_workspace_bytes(uint32_t n, int passes) {
 // aos = 0: keys/vals are separate u64 arrays (SoA).
 // aos = 1: keys/tmp_keys point at interleaved (key,val) 16-byte records;
 //          vals/tmp_vals ignored.
-// PBITS: digit width per pass. 7-bit digits double the per-digit write
-// burst (512 B at tile 4096) at the cost of more passes — the caller
-// picks per total bit count.
-template <int PBITS>
-static int onesweep_sort_tmpl(uintptr_t keys, uintptr_t vals,
-                              uintptr_t tmp_keys, uintptr_t tmp_vals,
-                              uint32_t n, int start_bit, int end_bit,
-                              uintptr_t ws, hipStream_t s, int aos,
-                              int sort_word = 0, uintptr_t fuse_recs = 0,
-                              uintptr_t fuse_out = 0,
-                              uint32_t fuse_rec_bytes = 0,
-                              uint64_t tie_run_mask = 0,
-                              uint64_t tie_lo_mask = 0,
-                              uint32_t* tie_flag = nullptr,
-                              uintptr_t fuse_segs = 0,
-                              uint32_t fuse_nsegs = 0) {
+static int onesweep_sort(uintptr_t keys, uintptr_t vals,
+                         uintptr_t tmp_keys, uintptr_t tmp_vals,
+                         uint32_t n, int start_bit, int end_bit,
+                         uintptr_t ws, hipStream_t s, int aos,
+                         int sort_word = 0, uintptr_t fuse_recs = 0,
+                         uintptr_t fuse_out = 0,
+                         uint32_t fuse_rec_bytes = 0,
+                         uint64_t tie_run_mask = 0,
+                         uint64_t tie_lo_mask = 0,
+                         uint32_t* tie_flag = nullptr,
+                         uintptr_t fuse_segs = 0,
+                         uint32_t fuse_nsegs = 0) {
+  constexpr int PBITS = 8;
   constexpr int PD = 1 << PBITS;
   // fusion is asked for by naming a record source: fuse_recs, or a
   // segment table (record_src), with which fuse_recs is unused and may be 0
   const bool want_fuse = fuse_recs || fuse_nsegs;
   if (fuse_nsegs && !fuse_segs)
     throw std::runtime_error("fused sort: nsegs without a table");
-  const int aos_tile = g_aos_tile;
-  uint32_t nb = aos ? os_num_tiles_t(n, aos_tile) : os_num_tiles(n);
+  uint32_t nb = os_num_tiles(n);
   int passes = (end_bit - start_bit + PBITS - 1) / PBITS;
   uint32_t* totals = reinterpret_cast<uint32_t*>(ws);
   uint64_t* key_dst = reinterpret_cast<uint64_t*>(totals + (size_t)passes * PD);
   uint64_t* val_dst = key_dst + PD;
   uint32_t* ticket = reinterpret_cast<uint32_t*>(val_dst + PD);
   uint64_t* desc = reinterpret_cast<uint64_t*>(ticket + 4);
-  const bool want_hist = g_sort_mode == 1 && aos && g_aos_tile == 4096 &&
-                         sort_word == 0;
-  if (!want_hist) {
-    HIP_CHECK(hipMemsetAsync(totals, 0, (size_t)passes * PD * 4, s));
-    uint32_t hist_grid = nb < 1024 ? (nb ? nb : 1) : 1024;
-    hipLaunchKernelGGL((onesweep_hist_all_kernel<10, PBITS>), dim3(hist_grid),
-                       dim3(BLOCK), 0, s,
-                       reinterpret_cast<const uint64_t*>(keys), n, start_bit,
-                       passes, totals, aos ? 2 : 1, sort_word);
-    HIP_CHECK(hipGetLastError());
-  }
-  size_t lds_soa = (size_t)BLOCK * OS_ITEMS * 8 + (size_t)NW * PD * 4 +
-                   PD * 4 * 2 + BLOCK * 4 + 16 + BLOCK * OS_ITEMS;
-  const int se = g_split_exch > 1 ? g_split_exch : 1;
-  size_t lds_aos = (size_t)aos_tile * 16 / se +
-                   (size_t)(512 / kWave) * PD * 4 + PD * 4 * 2 + 512 * 4 + 16;
+  HIP_CHECK(hipMemsetAsync(totals, 0, (size_t)passes * PD * 4, s));
+  uint32_t hist_grid = nb < 1024 ? (nb ? nb : 1) : 1024;
+  hipLaunchKernelGGL((onesweep_hist_all_kernel<10, PBITS>), dim3(hist_grid),
+                     dim3(BLOCK), 0, s,
+                     reinterpret_cast<const uint64_t*>(keys), n, start_bit,
+                     passes, totals, aos ? 2 : 1, sort_word);
+  HIP_CHECK(hipGetLastError());
+  size_t lds_soa = (size_t)OS_TILE * 8 + (size_t)NW * PD * 4 +
+                   PD * 4 * 2 + BLOCK * 4 + 16 + OS_TILE;
+  size_t lds_aos = (size_t)OS_TILE * 16 +
+                   (size_t)(OS_AOS_BS / kWave) * PD * 4 + PD * 4 * 2 +
+                   OS_AOS_BS * 4 + 16;
   size_t lds = aos ? lds_aos : lds_soa;
   static bool attr_set = false;
   if (!attr_set) {
     for (const void* f :
          {reinterpret_cast<const void*>(
-              &onesweep_pass_kernel<true, OS_ITEMS, false, BLOCK, PBITS>),
+              &onesweep_pass_kernel<true, OS_ITEMS, false, BLOCK>),
           reinterpret_cast<const void*>(
-              &onesweep_pass_kernel<false, OS_ITEMS, false, BLOCK, PBITS>),
+              &onesweep_pass_kernel<false, OS_ITEMS, false, BLOCK>),
           reinterpret_cast<const void*>(
-              &onesweep_pass_kernel<true, 4, true, 512, PBITS>),
+              &onesweep_pass_kernel<true, OS_AOS_ITEMS, true, OS_AOS_BS>),
           reinterpret_cast<const void*>(
-              &onesweep_pass_kernel<true, 8, true, 512, PBITS>),
-          reinterpret_cast<const void*>(
-              &onesweep_pass_kernel<true, 16, true, 512, PBITS>),
-          reinterpret_cast<const void*>(
-              &onesweep_pass_kernel<true, 8, true, 512, PBITS, true>),
-          reinterpret_cast<const void*>(
-              &onesweep_pass_kernel<true, 8, true, 512, PBITS, false,
+              &onesweep_pass_kernel<true, OS_AOS_ITEMS, true, OS_AOS_BS,
                                     true>)})
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 160 * 1024 - 1024);
     attr_set = true;
   }
-  // hist mode: reuse the desc area as [hist u32[nb*PD] | scan partials]
-  const bool use_hist = want_hist;
-  uint32_t* hist32 = reinterpret_cast<uint32_t*>(desc);
-  uint32_t* hist_scan_ws = hist32 + (size_t)nb * PD;
   uintptr_t src_k = keys, src_v = vals, dst_k = tmp_keys, dst_v = tmp_vals;
   int cur = 0;
   for (int p = 0; p < passes; ++p) {
@@ -1838,29 +1691,16 @@ static int onesweep_sort_tmpl(uintptr_t keys, uintptr_t vals,
     if (sb > 64 - PBITS) sb = 64 - PBITS;  // same clamp as hist_all
     // fused final pass: the writeout copies whole records to fuse_out
     // (the gather folded into the sort — key_dst becomes record bases)
-    // (not in hist+scan mode: the fused kernel walks lookback descriptors,
-    // which that mode never resets — the caller falls back via -1)
-    const bool fuse = want_fuse && p == passes - 1 && aos &&
-                      aos_tile == 4096 && g_split_exch <= 1 && !g_lean &&
-                      !want_hist;
-    if (use_hist) {
-      hist_launch<PBITS>(reinterpret_cast<const uint64_t*>(src_k), n, sb,
-                         hist32, s, 0, 2);
-      scan_launch<PBITS>(hist32, nb, hist_scan_ws, totals + (size_t)p * PD,
-                         s);
-    }
+    const bool fuse = want_fuse && aos && p == passes - 1;
     hipLaunchKernelGGL((onesweep_digit_bases_kernel<PD>), dim3(1),
                        dim3(BLOCK), 0, s, totals, p,
                        fuse ? (uint64_t)fuse_out : (uint64_t)dst_k,
                        fuse ? 0 : (uint64_t)dst_v, key_dst, val_dst,
                        fuse ? (int)fuse_rec_bytes : (aos ? 16 : 8));
     HIP_CHECK(hipGetLastError());
-    if (!use_hist) {
-      HIP_CHECK(hipMemsetAsync(ticket, 0, 16, s));
-      HIP_CHECK(hipMemsetAsync(desc, 0, (size_t)nb * PD * 8, s));
-    }
-    const uint32_t* pass_pref = use_hist ? hist32 : nullptr;
-    if (fuse) {   // (ticket/desc were reset in the !use_hist block)
+    HIP_CHECK(hipMemsetAsync(ticket, 0, 16, s));
+    HIP_CHECK(hipMemsetAsync(desc, 0, (size_t)nb * PD * 8, s));
+    if (fuse) {
       if (tie_flag) {
         // truncated sort: the passes so far ordered the pairs by the run
         // bits only; put the tied runs in order before the final digit
@@ -1871,65 +1711,42 @@ static int onesweep_sort_tmpl(uintptr_t keys, uintptr_t vals,
         HIP_CHECK(hipGetLastError());
       }
       hipLaunchKernelGGL(
-          (onesweep_pass_kernel<true, 8, true, 512, PBITS, false, true>),
-          dim3(nb), dim3(512), lds, s,
+          (onesweep_pass_kernel<true, OS_AOS_ITEMS, true, OS_AOS_BS, true>),
+          dim3(nb), dim3(OS_AOS_BS), lds, s,
           reinterpret_cast<const uint64_t*>(src_k), nullptr, n, sb, desc,
-          ticket, key_dst, val_dst, g_pass_stage, nullptr, nullptr,
-          sort_word, g_lb_mode, 0,
+          ticket, key_dst, val_dst, nullptr, sort_word,
           reinterpret_cast<const uint32_t*>(fuse_recs),
           fuse_rec_bytes / 4,
           reinterpret_cast<const RecSegment*>(fuse_segs), fuse_nsegs);
       HIP_CHECK(hipGetLastError());
       return cur;  // records land in fuse_out; pair buffers are dead
-    } else if (aos && aos_tile == 8192) {
-      hipLaunchKernelGGL((onesweep_pass_kernel<true, 16, true, 512, PBITS>),
-                         dim3(nb), dim3(512), lds, s,
-                         reinterpret_cast<const uint64_t*>(src_k), nullptr, n,
-                         sb, desc, ticket, key_dst, val_dst, g_pass_stage,
-                         g_timing_buf, pass_pref, sort_word, g_lb_mode,
-                         g_split_exch);
-    } else if (aos && aos_tile == 2048) {
-      hipLaunchKernelGGL((onesweep_pass_kernel<true, 4, true, 512, PBITS>),
-                         dim3(nb), dim3(512), lds, s,
-                         reinterpret_cast<const uint64_t*>(src_k), nullptr, n,
-                         sb, desc, ticket, key_dst, val_dst, g_pass_stage,
-                         g_timing_buf, pass_pref, sort_word, g_lb_mode,
-                         g_split_exch);
-    } else if (aos && g_lean) {
-      hipLaunchKernelGGL(
-          (onesweep_pass_kernel<true, 8, true, 512, PBITS, true>),
-          dim3(nb), dim3(512), lds, s,
-          reinterpret_cast<const uint64_t*>(src_k), nullptr, n,
-          sb, desc, ticket, key_dst, val_dst, g_pass_stage,
-          g_timing_buf, pass_pref, sort_word, g_lb_mode, g_split_exch);
     } else if (aos) {
-      hipLaunchKernelGGL((onesweep_pass_kernel<true, 8, true, 512, PBITS>),
-                         dim3(nb), dim3(512), lds, s,
-                         reinterpret_cast<const uint64_t*>(src_k), nullptr, n,
-                         sb, desc, ticket, key_dst, val_dst, g_pass_stage,
-                         g_timing_buf, pass_pref, sort_word, g_lb_mode,
-                         g_split_exch);
+      hipLaunchKernelGGL(
+          (onesweep_pass_kernel<true, OS_AOS_ITEMS, true, OS_AOS_BS>),
+          dim3(nb), dim3(OS_AOS_BS), lds, s,
+          reinterpret_cast<const uint64_t*>(src_k), nullptr, n, sb, desc,
+          ticket, key_dst, val_dst, g_timing_buf, sort_word);
     } else if (vals) {
       hipLaunchKernelGGL(
-          (onesweep_pass_kernel<true, OS_ITEMS, false, BLOCK, PBITS>),
+          (onesweep_pass_kernel<true, OS_ITEMS, false, BLOCK>),
           dim3(nb), dim3(BLOCK), lds, s,
           reinterpret_cast<const uint64_t*>(src_k),
           reinterpret_cast<const uint64_t*>(src_v), n, sb, desc, ticket,
-          key_dst, val_dst, 3, nullptr, nullptr, 0, g_lb_mode);
+          key_dst, val_dst);
     } else {
       hipLaunchKernelGGL(
-          (onesweep_pass_kernel<false, OS_ITEMS, false, BLOCK, PBITS>),
+          (onesweep_pass_kernel<false, OS_ITEMS, false, BLOCK>),
           dim3(nb), dim3(BLOCK), lds, s,
           reinterpret_cast<const uint64_t*>(src_k), nullptr, n, sb, desc,
-          ticket, key_dst, val_dst, 3, nullptr, nullptr, 0, g_lb_mode);
+          ticket, key_dst, val_dst);
     }
     HIP_CHECK(hipGetLastError());
     std::swap(src_k, dst_k);
     std::swap(src_v, dst_v);
     cur ^= 1;
   }
-  // a requested fusion that no pass applied (non-default tile/ablation
-  // modes) must NOT silently leave `out` unwritten — caller falls back
+  // a requested fusion with no pass to apply it in (end_bit == start_bit)
+  // must NOT silently leave `out` unwritten — the caller falls back
   if (want_fuse) return -1;
   return cur;
 }
@@ -1938,16 +1755,15 @@ int onesweep_sort_pairs_u64(uintptr_t keys, uintptr_t vals,
                             uintptr_t tmp_keys, uintptr_t tmp_vals,
                             uint32_t n, int start_bit, int end_bit,
                             uintptr_t ws, uintptr_t stream) {
-  return onesweep_sort_tmpl<8>(keys, vals, tmp_keys, tmp_vals, n, start_bit,
-                               end_bit, ws,
-                               reinterpret_cast<hipStream_t>(stream), 0);
+  return onesweep_sort(keys, vals, tmp_keys, tmp_vals, n, start_bit, end_bit,
+                       ws, reinterpret_cast<hipStream_t>(stream), 0);
 }
 
 int onesweep_sort_aos_u64(uintptr_t pairs, uintptr_t tmp_pairs, uint32_t n,
                           int start_bit, int end_bit, uintptr_t ws,
                           uintptr_t stream) {
-  return onesweep_sort_tmpl<8>(pairs, 0, tmp_pairs, 0, n, start_bit, end_bit,
-                               ws, reinterpret_cast<hipStream_t>(stream), 1);
+  return onesweep_sort(pairs, 0, tmp_pairs, 0, n, start_bit, end_bit, ws,
+                       reinterpret_cast<hipStream_t>(stream), 1);
 }
 
 // sort_word = 1: pairs order by their SECOND u64's bits (the aux word of
@@ -1957,9 +1773,8 @@ int onesweep_sort_aos_word_u64(uintptr_t pairs, uintptr_t tmp_pairs,
                                uint32_t n, int start_bit, int end_bit,
                                uintptr_t ws, uintptr_t stream,
                                int sort_word) {
-  return onesweep_sort_tmpl<8>(pairs, 0, tmp_pairs, 0, n, start_bit, end_bit,
-                               ws, reinterpret_cast<hipStream_t>(stream), 1,
-                               sort_word);
+  return onesweep_sort(pairs, 0, tmp_pairs, 0, n, start_bit, end_bit, ws,
+                       reinterpret_cast<hipStream_t>(stream), 1, sort_word);
 }
 
 // sort + FUSED final gather: records land sorted in `out` (the last
@@ -1972,10 +1787,9 @@ int onesweep_sort_aos_fused_u64(uintptr_t pairs, uintptr_t tmp_pairs,
                                 int sort_word, uintptr_t recs,
                                 uintptr_t out, uint32_t rec_bytes,
                                 uintptr_t segs, uint32_t nsegs) {
-  return onesweep_sort_tmpl<8>(pairs, 0, tmp_pairs, 0, n, start_bit, end_bit,
-                               ws, reinterpret_cast<hipStream_t>(stream), 1,
-                               sort_word, recs, out, rec_bytes, 0, 0,
-                               nullptr, segs, nsegs);
+  return onesweep_sort(pairs, 0, tmp_pairs, 0, n, start_bit, end_bit, ws,
+                       reinterpret_cast<hipStream_t>(stream), 1, sort_word,
+                       recs, out, rec_bytes, 0, 0, nullptr, segs, nsegs);
 }
 
 // ---------------------------------------------------------------------------
@@ -2016,8 +1830,7 @@ void sort_records_plan(uint32_t n, int end_bit, int* lo_bit, int* passes,
 
 // Sorts the extracted pairs and writes the sorted RECORDS to `out`.
 // Returns the path taken (1 or 2), or -1 having done nothing when the
-// truncated sort is bypassed — `fuse` off, tie repair off, no plan, or
-// any ablation global under which the fused final pass does not apply —
+// truncated sort is bypassed — `fuse` off, tie repair off, or no plan —
 // and the caller runs the full sequence itself. ws must be sized for the
 // full sequence (ceil(end_bit / 8) + 2 aux passes): the overflow flag
 // lives in the totals rows the shorter plan leaves unused.
@@ -2030,9 +1843,7 @@ int sort_records_truncated_u64(uintptr_t pairs, uintptr_t tmp_pairs,
                                uint32_t nsegs) {
   g_last_sort_path = 0;
   if (end_bit > 64) end_bit = 64;
-  if (!fuse || !g_tie_repair || n == 0 || g_aos_tile != 4096 ||
-      g_split_exch > 1 || g_lean || g_sort_mode != 0)
-    return -1;
+  if (!fuse || !g_tie_repair || n == 0) return -1;
   int lo_bit, passes, run_bits;
   sort_records_plan(n, end_bit, &lo_bit, &passes, &run_bits);
   if (passes == 0) return -1;
@@ -2044,10 +1855,11 @@ int sort_records_truncated_u64(uintptr_t pairs, uintptr_t tmp_pairs,
   uint32_t* flag = reinterpret_cast<uint32_t*>(
       ws + onesweep_workspace_bytes(n, passes));
   HIP_CHECK(hipMemsetAsync(flag, 0, 4, s));
-  int cur = onesweep_sort_tmpl<8>(pairs, 0, tmp_pairs, 0, n, lo_bit, end_bit,
-                                  ws, s, 1, 0, recs, out, rec_bytes,
-                                  run_mask, lo_mask, flag, segs, nsegs);
-  if (cur < 0) throw std::runtime_error("truncated sort: fusion refused");
+  int cur = onesweep_sort(pairs, 0, tmp_pairs, 0, n, lo_bit, end_bit, ws, s,
+                          1, 0, recs, out, rec_bytes, run_mask, lo_mask,
+                          flag, segs, nsegs);
+  // both fused calls here cover >= 2 digits (passes != 0), so they ran
+  if (cur < 0) throw std::runtime_error("truncated sort: no pass ran");
   uint32_t overflow = 0;
   HIP_CHECK(hipMemcpyAsync(&overflow, flag, 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
@@ -2058,20 +1870,12 @@ int sort_records_truncated_u64(uintptr_t pairs, uintptr_t tmp_pairs,
   // simply overwritten.
   if (cur == 1) std::swap(pairs, tmp_pairs);
   if (key_bytes > 8 &&
-      onesweep_sort_tmpl<8>(pairs, 0, tmp_pairs, 0, n, 48, 64, ws, s, 1, 1))
+      onesweep_sort(pairs, 0, tmp_pairs, 0, n, 48, 64, ws, s, 1, 1))
     std::swap(pairs, tmp_pairs);
-  if (onesweep_sort_tmpl<8>(pairs, 0, tmp_pairs, 0, n, 0, end_bit, ws, s, 1,
-                            0, recs, out, rec_bytes, 0, 0, nullptr, segs,
-                            nsegs) < 0)
-    throw std::runtime_error("sort fallback: fusion refused");
+  if (onesweep_sort(pairs, 0, tmp_pairs, 0, n, 0, end_bit, ws, s, 1, 0, recs,
+                    out, rec_bytes, 0, 0, nullptr, segs, nsegs) < 0)
+    throw std::runtime_error("sort fallback: no pass ran");
   return g_last_sort_path = 2;
-}
-
-int onesweep_sort_aos7_u64(uintptr_t pairs, uintptr_t tmp_pairs, uint32_t n,
-                           int start_bit, int end_bit, uintptr_t ws,
-                           uintptr_t stream) {
-  return onesweep_sort_tmpl<7>(pairs, 0, tmp_pairs, 0, n, start_bit, end_bit,
-                               ws, reinterpret_cast<hipStream_t>(stream), 1);
 }
 
 int sort_pairs_u64(uintptr_t keys, uintptr_t vals, uintptr_t tmp_keys,

@@ -112,7 +112,6 @@ def partition_aos(keys: torch.Tensor, vals: torch.Tensor, nbits: int,
 
 def sort_pairs_aos(pairs: torch.Tensor, start_bit: int = 0,
                    end_bit: int = 64,
-                   digit_bits: Optional[int] = None,
                    tmp: Optional[torch.Tensor] = None,
                    ws: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Sort interleaved (key u64, val u64) 16-byte records by key bits
@@ -126,11 +125,7 @@ def sort_pairs_aos(pairs: torch.Tensor, start_bit: int = 0,
     if n == 0:
         return pairs
     bits = min(end_bit, 64) - start_bit
-    if digit_bits is None:
-        # measured: 7-bit digits (512 B bursts) do NOT beat 8-bit — the
-        # write-only burst model overestimates; pass floor is elsewhere
-        digit_bits = 8
-    passes = -(-bits // digit_bits)
+    passes = -(-bits // 8)
     if tmp is None:
         tmp = torch.empty_like(pairs)
     else:
@@ -141,10 +136,9 @@ def sort_pairs_aos(pairs: torch.Tensor, start_bit: int = 0,
         ws = torch.empty(need_ws, dtype=torch.uint8, device=pairs.device)
     else:
         assert ws.numel() >= need_ws, "ws too small"
-    fn = (m.onesweep_sort_aos7_u64 if digit_bits == 7
-          else m.onesweep_sort_aos_u64)
-    res = fn(pairs.data_ptr(), tmp.data_ptr(), n, start_bit,
-             start_bit + bits, ws.data_ptr(), _stream())
+    res = m.onesweep_sort_aos_u64(pairs.data_ptr(), tmp.data_ptr(), n,
+                                  start_bit, start_bit + bits, ws.data_ptr(),
+                                  _stream())
     return pairs if res == 0 else tmp
 
 
@@ -274,7 +268,7 @@ def sort_records(recs, rec_bytes: int, key_bytes: int = 8,
     output is the one a contiguous copy would give. The memory behind the
     pointers must stay valid until the sort has run on the stream.
 
-    With ``fuse`` and the default kernel configuration the call BLOCKS on
+    With ``fuse`` and tie repair on (the default) the call BLOCKS on
     the current stream once: the truncated sort reads back a flag that
     says whether the full pass sequence must run after all. ``ws``, when
     given, must be sized for the full sequence (as computed below).
@@ -331,8 +325,8 @@ def sort_records(recs, rec_bytes: int, key_bytes: int = 8,
     # truncated sort (kernels.hip sort_records_truncated_u64): LSD over the
     # leading key bits only, tied runs repaired in LDS, full sequence as
     # the fallback for inputs with long runs. -1 = bypassed (fuse off, tie
-    # repair off, no plan for this n/end_bit, or an ablation global set):
-    # nothing ran, take the full sequence below. Path: last_sort_path().
+    # repair off, or no plan for this n/end_bit): nothing ran, take the
+    # full sequence below. Path: last_sort_path().
     if m.sort_records_truncated_u64(
             cur.data_ptr(), other.data_ptr(), n, min(end_bit, 64),
             key_bytes, ws.data_ptr(), _stream(), recs_ptr,
@@ -348,8 +342,8 @@ def sort_records(recs, rec_bytes: int, key_bytes: int = 8,
     if fuse:
         # the FINAL prefix pass writes whole records (kernels.hip
         # FUSE_GATHER): the last pair writeout + the separate gather's
-        # pair re-read disappear. -1 = fusion not applicable under the
-        # current ablation globals -> fall through to the plain path
+        # pair re-read disappear. -1 = no pass ran at all (end_bit == 0)
+        # -> fall through to the plain path, whose gather writes `out`
         res = m.onesweep_sort_aos_fused_u64(
             cur.data_ptr(), other.data_ptr(), n, 0, min(end_bit, 64),
             ws.data_ptr(), _stream(), 0, recs_ptr,

@@ -210,18 +210,3 @@ def test_fused_sort_stable_on_equal_prefixes(hs, key_bytes):
     arr = _equal_prefix_records(rng, n, W)
     want = _sort_oracle(arr, key_bytes)
     assert np.array_equal(_sort_guarded(arr, W, key_bytes, fuse=True), want)
-
-
-def test_fused_sort_in_hist_scan_mode(hs):
-    """set_sort_mode(1) never resets the lookback descriptors, so a fused
-    sort must fall back to the plain path and still give the oracle."""
-    rng = np.random.default_rng(5)
-    n, W = 3 * 4096 + 17, 100
-    arr = _records(rng, n, W)
-    want = _sort_oracle(arr, 10)
-    hs.set_sort_mode(1)
-    try:
-        got = _sort_guarded(arr, W, 10, fuse=True)
-    finally:
-        hs.set_sort_mode(0)
-    assert np.array_equal(got, want)
