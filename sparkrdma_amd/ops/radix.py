@@ -9,6 +9,7 @@ from __future__ import annotations
 
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import load
@@ -18,6 +19,47 @@ from ..aggregate import AGGREGATORS as REDUCE_OPS
 
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+def digit_counts(src: int, n: int, shift: int, nbits_eff: int, device,
+                 func: int = 0, in_stride: int = 1, nparts: int = 0,
+                 totals: Optional[torch.Tensor] = None
+                 ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """radix_hist + radix_scan over the n u64 keys at device address
+    ``src`` (``in_stride`` u64 apart). Returns (hist, totals): the scanned
+    per-tile histogram for the scatter of the same digit, and the
+    int32[2^nbits_eff] digit totals (in ``totals`` when supplied).
+
+    The stream is torch's current one, taken here and not passed in: the
+    scan workspace is dropped on return while the scan may still be
+    queued, which is safe only because the caching allocator orders reuse
+    of a freed block on the current stream — the stream launched on."""
+    m = load()
+    hist = torch.empty(m.radix_hist_bytes(n, nbits_eff) // 4,
+                       dtype=torch.int32, device=device)
+    scan_ws = torch.empty(m.radix_scan_ws_bytes(n, nbits_eff) // 4,
+                          dtype=torch.int32, device=device)
+    if totals is None:
+        totals = torch.empty(1 << nbits_eff, dtype=torch.int32, device=device)
+    s = _stream()
+    m.radix_hist(src, n, shift, nbits_eff, hist.data_ptr(), s, func,
+                 in_stride, nparts)
+    m.radix_scan(hist.data_ptr(), n, nbits_eff, totals.data_ptr(),
+                 scan_ws.data_ptr(), s)
+    return hist, totals
+
+
+def scatter_pairs(pairs: torch.Tensor, n: int, shift: int, nbits_eff: int,
+                  hist: torch.Tensor, dst_addr: torch.Tensor,
+                  func: int = 0, nparts: int = 0) -> None:
+    """Group n interleaved 16-byte (key, aux) pairs by the digit of the
+    key into contiguous per-digit runs: digit d's run starts at the device
+    byte address ``dst_addr[d]`` (int64[2^nbits_eff] on the device).
+    ``hist`` is digit_counts' for the same pairs and digit."""
+    val_dst = dst_addr + 8
+    load().radix_scatter(pairs.data_ptr(), pairs.data_ptr() + 8, n, shift,
+                         nbits_eff, hist.data_ptr(), dst_addr.data_ptr(),
+                         val_dst.data_ptr(), _stream(), func, 1, 2, nparts)
 
 
 def radix_partition(keys: torch.Tensor, vals: Optional[torch.Tensor],
@@ -44,18 +86,10 @@ def radix_partition(keys: torch.Tensor, vals: Optional[torch.Tensor],
     nbits_eff = max(nbits, 4)  # kernel instantiations start at 4 bits; the
     nd = 1 << nbits_eff        # extra mask bits read zeros above the digit
     dev = keys.device
-    hist = torch.empty(m.radix_hist_bytes(n, nbits_eff) // 4,
-                       dtype=torch.int32, device=dev)
-    scan_ws = torch.empty(m.radix_scan_ws_bytes(n, nbits_eff) // 4,
-                          dtype=torch.int32, device=dev)
-    totals = torch.empty(nd, dtype=torch.int32, device=dev)
     if hash_mix and nbits_eff != nbits:
         raise ValueError("hash partitioning requires nbits >= 4")
-    s = _stream()
-    m.radix_hist(keys.data_ptr(), n, shift, nbits_eff, hist.data_ptr(), s,
-                 int(hash_mix))
-    m.radix_scan(hist.data_ptr(), n, nbits_eff, totals.data_ptr(),
-                 scan_ws.data_ptr(), s)
+    hist, totals = digit_counts(keys.data_ptr(), n, shift, nbits_eff, dev,
+                                int(hash_mix))
     keys_out = vals_out = None
     if key_dst is None:
         counts64 = totals.to(torch.int64)
@@ -70,7 +104,8 @@ def radix_partition(keys: torch.Tensor, vals: Optional[torch.Tensor],
     m.radix_scatter(keys.data_ptr(),
                     vals.data_ptr() if vals is not None else 0,
                     n, shift, nbits_eff, hist.data_ptr(),
-                    key_dst.data_ptr(), val_dst.data_ptr(), s, int(hash_mix))
+                    key_dst.data_ptr(), val_dst.data_ptr(), _stream(),
+                    int(hash_mix))
     return totals[:1 << nbits], keys_out, vals_out
 
 
@@ -87,18 +122,9 @@ def partition_aos(keys: torch.Tensor, vals: torch.Tensor, nbits: int,
     if shift is None:
         shift = 64 - nbits
     nbits_eff = max(nbits, 4)
-    nd = 1 << nbits_eff
     dev = keys.device
-    hist = torch.empty(m.radix_hist_bytes(n, nbits_eff) // 4,
-                       dtype=torch.int32, device=dev)
-    scan_ws = torch.empty(m.radix_scan_ws_bytes(n, nbits_eff) // 4,
-                          dtype=torch.int32, device=dev)
-    totals = torch.empty(nd, dtype=torch.int32, device=dev)
-    s = _stream()
-    m.radix_hist(keys.data_ptr(), n, shift, nbits_eff, hist.data_ptr(), s,
-                 int(hash_mix))
-    m.radix_scan(hist.data_ptr(), n, nbits_eff, totals.data_ptr(),
-                 scan_ws.data_ptr(), s)
+    hist, totals = digit_counts(keys.data_ptr(), n, shift, nbits_eff, dev,
+                                int(hash_mix))
     pairs = torch.empty(2 * n, dtype=torch.int64, device=dev)
     counts64 = totals.to(torch.int64)
     bases = torch.cumsum(counts64, 0) - counts64
@@ -106,7 +132,7 @@ def partition_aos(keys: torch.Tensor, vals: torch.Tensor, nbits: int,
     val_dst = key_dst + 8
     m.radix_scatter(keys.data_ptr(), vals.data_ptr(), n, shift, nbits_eff,
                     hist.data_ptr(), key_dst.data_ptr(), val_dst.data_ptr(),
-                    s, int(hash_mix), 1)
+                    _stream(), int(hash_mix), 1)
     return totals[:1 << nbits], pairs
 
 
@@ -202,9 +228,16 @@ def reduce_by_key_aos(pairs: torch.Tensor, op: str,
 
 
 def extract_pairs(recs: torch.Tensor, rec_bytes: int, key_bytes: int = 8,
-                  pairs: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  pairs: Optional[torch.Tensor] = None,
+                  bounds: Optional[torch.Tensor] = None,
+                  pid: tuple = ()) -> torch.Tensor:
     """records -> interleaved (key-prefix u64, aux u64) pairs, where
-    aux = key_lo16 << 48 | record_index (kernels.hip extract_pairs)."""
+    aux = key_lo16 << 48 | record_index (kernels.hip extract_pairs).
+
+    The write path can have pair.x hold the record's partition id instead
+    of the prefix: ``bounds`` (int64 device split points, func 4) are
+    searched per record (bounds.hip); else ``pid`` = (func, shift, mask,
+    nparts) applies that partition function to the prefix."""
     m = load()
     n = recs.numel() // rec_bytes
     if pairs is None:
@@ -212,8 +245,13 @@ def extract_pairs(recs: torch.Tensor, rec_bytes: int, key_bytes: int = 8,
     else:
         assert pairs.numel() >= 2 * n
         pairs = pairs[:2 * n]
-    m.extract_pairs(recs.data_ptr(), n, rec_bytes, key_bytes,
-                    pairs.data_ptr(), _stream())
+    if bounds is not None:
+        m.extract_pairs_bounds(recs.data_ptr(), n, rec_bytes, key_bytes,
+                               pairs.data_ptr(), bounds.data_ptr(),
+                               bounds.numel(), _stream())
+    else:
+        m.extract_pairs(recs.data_ptr(), n, rec_bytes, key_bytes,
+                        pairs.data_ptr(), _stream(), *pid)
     return pairs
 
 
@@ -361,6 +399,42 @@ def sort_records(recs, rec_bytes: int, key_bytes: int = 8,
     return out
 
 
+def gather_grouped(recs: torch.Tensor, pairs_grouped: torch.Tensor, n: int,
+                   rec_bytes: int, counts: np.ndarray, dst_addr: np.ndarray,
+                   shift: int, mask: int, func: int = 0,
+                   nparts: int = 0) -> None:
+    """The one gather of the partition path: pairs_grouped[j] names the
+    record that moves to dst_addr[d] + (j - start[d]) * rec_bytes, where d
+    is the digit of its key under (shift, mask, func, nparts) and start
+    the exclusive sum of ``counts``. ``counts`` / ``dst_addr``: int64
+    numpy, one entry per digit; dst_addr holds device byte addresses."""
+    dev = recs.device
+    starts = np.cumsum(counts) - counts
+    dstart_t = torch.from_numpy(starts.astype(np.uint32)
+                                .view(np.int32)).to(dev)
+    dst_addr_t = torch.from_numpy(dst_addr).to(dev)
+    load().gather_records(recs.data_ptr(), pairs_grouped.data_ptr(), n,
+                          rec_bytes, 1, 0, dst_addr_t.data_ptr(),
+                          dstart_t.data_ptr(), shift, mask, func, nparts,
+                          _stream())
+
+
+def group_records(recs: torch.Tensor, rec_bytes: int, pairs: torch.Tensor,
+                  n: int, shift: int, nbits_eff: int, hist: torch.Tensor,
+                  counts: np.ndarray, dst_addr: np.ndarray, func: int = 0,
+                  nparts: int = 0) -> None:
+    """Single-pass tail of a record partition, after digit_counts and the
+    caller's layout: group the pairs by digit (scatter_pairs), then move
+    digit d's records, in input order, to dst_addr[d] onward
+    (gather_grouped). ``counts`` are all 2^nbits_eff digit totals."""
+    pairs_out = torch.empty_like(pairs)
+    starts_t = torch.from_numpy(np.cumsum(counts) - counts).to(recs.device)
+    scatter_pairs(pairs, n, shift, nbits_eff, hist,
+                  pairs_out.data_ptr() + starts_t * 16, func, nparts)
+    gather_grouped(recs, pairs_out, n, rec_bytes, counts, dst_addr, shift,
+                   (1 << nbits_eff) - 1, func, nparts)
+
+
 def partition_records(recs: torch.Tensor, rec_bytes: int,
                       key_bytes: int = 8, nbits: int = 8,
                       shift: Optional[int] = None, func: int = 0,
@@ -368,42 +442,18 @@ def partition_records(recs: torch.Tensor, rec_bytes: int,
     """Group W-byte records into 2^nbits contiguous buckets (digit from
     the key prefix) — the stage-mode (RCCL alltoall) send-buffer builder
     for wide records. Returns (counts int64 numpy, grouped records)."""
-    m = load()
     n = recs.numel() // rec_bytes
     if shift is None:
         shift = 64 - nbits
     nbits_eff = max(nbits, 4)
-    nd = 1 << nbits_eff
-    dev = recs.device
-    s = _stream()
     pairs = extract_pairs(recs, rec_bytes, key_bytes)
-    hist = torch.empty(m.radix_hist_bytes(n, nbits_eff) // 4,
-                       dtype=torch.int32, device=dev)
-    scan_ws = torch.empty(m.radix_scan_ws_bytes(n, nbits_eff) // 4,
-                          dtype=torch.int32, device=dev)
-    totals = torch.empty(nd, dtype=torch.int32, device=dev)
-    m.radix_hist(pairs.data_ptr(), n, shift, nbits_eff, hist.data_ptr(), s,
-                 func, 2, nparts)
-    m.radix_scan(hist.data_ptr(), n, nbits_eff, totals.data_ptr(),
-                 scan_ws.data_ptr(), s)
-    import numpy as np
+    hist, totals = digit_counts(pairs.data_ptr(), n, shift, nbits_eff,
+                                recs.device, func, 2, nparts)
     counts = totals.cpu().numpy().astype(np.int64)  # syncs the stream
-    starts = np.zeros(nd, dtype=np.int64)
-    np.cumsum(counts[:-1], out=starts[1:])
-    pairs_out = torch.empty_like(pairs)
-    bases_t = torch.from_numpy(starts).to(dev)
-    kd = pairs_out.data_ptr() + bases_t * 16
-    vd = kd + 8
-    m.radix_scatter(pairs.data_ptr(), pairs.data_ptr() + 8, n, shift,
-                    nbits_eff, hist.data_ptr(), kd.data_ptr(),
-                    vd.data_ptr(), s, func, 1, 2, nparts)
     out = torch.empty_like(recs)
-    dstart_t = torch.from_numpy(starts.astype(np.uint32)
-                                .view(np.int32)).to(dev)
-    dst_addr_t = out.data_ptr() + bases_t * rec_bytes
-    m.gather_records(recs.data_ptr(), pairs_out.data_ptr(), n, rec_bytes,
-                     1, 0, dst_addr_t.data_ptr(), dstart_t.data_ptr(),
-                     shift, nd - 1, func, nparts, s)
+    dst = out.data_ptr() + (np.cumsum(counts) - counts) * rec_bytes
+    group_records(recs, rec_bytes, pairs, n, shift, nbits_eff, hist, counts,
+                  dst, func, nparts)
     return counts[:1 << nbits], out
 
 

@@ -15,7 +15,7 @@ kernel-side partition function (kernels.hip ``PartFunc``):
                                              split points, unsigned compare)
 Funcs 2/3 lift the r01 pow2-only restriction. The LDS counter layout
 caps ONE kernel pass at 2^12 digits; the writer runs a two-level
-coarse/fine pid radix for 4096 < R <= 2^24 (writer._commit_gpu_records).
+coarse/fine pid radix for 4096 < R <= 2^24 (writer._group_pairs_2level).
 Func 4 is not a ``PartFunc`` of the hist/scatter/gather kernels: the
 search over ``gpu_bounds()`` runs once per record in
 extract_pairs_bounds (ops/csrc/bounds.hip), which leaves the partition id

@@ -12,7 +12,10 @@ from the layout, and publishing is a one-sided 12-byte write.
 Block chunking keeps the reference policy (RdmaMappedFile.java:113-157):
 partitions are packed greedily into ~shuffle_write_block_size blocks, split
 only at partition boundaries, so every partition is one contiguous
-(addr, len) range.
+(addr, len) range. ``group_partitions`` is that policy for all three
+lanes; the two GPU lanes (16-byte direct scatter, wide-record gather)
+share one placement and publication step, ``_GpuLayout``, and differ only
+in the kernels that write to the addresses it hands out.
 
 Record model (fixed-width path): a partition segment is AoS —
 ``[key u64 | value bytes] × n`` interleaved records (doubles the GPU
@@ -65,6 +68,107 @@ def unpack_partition_segment(buf, value_width: int):
     return keys, values
 
 
+def group_partitions(seg_bytes, write_block: int) -> List[List[int]]:
+    """The block policy of every lane: partitions are taken in order and a
+    group (one pool block) is closed before the partition that would push
+    it past ``write_block``. A group is never empty, so a partition larger
+    than ``write_block`` is a group of its own."""
+    groups: List[List[int]] = []
+    group: List[int] = []
+    group_bytes = 0
+    for p, nb in enumerate(seg_bytes):
+        if group and group_bytes + nb > write_block:
+            groups.append(group)
+            group, group_bytes = [], 0
+        group.append(p)
+        group_bytes += int(nb)
+    if group:
+        groups.append(group)
+    return groups
+
+
+class _GpuLayout:
+    """Where a GPU lane's kernel writes each partition of one map output.
+
+    Construction places the groups of ``seg_bytes`` (int64 bytes per
+    partition) in HBM pool blocks and fills the location table. A group
+    the pool cannot serve spills (the reference keeps a disk file path for
+    overflow — SURVEY §7.1 RdmaMappedFile row): its partitions go to one
+    transient device staging tensor, and ``finish`` copies them to a host
+    pool block. ``dst`` (int64[nd], the table the kernel indexes by digit)
+    holds the device byte address of every non-empty partition, in HBM or
+    in the staging tensor; 0 for empty partitions and digits >= R."""
+
+    def __init__(self, writer: "ShuffleWriter", seg_bytes: np.ndarray,
+                 nd: int, device):
+        import torch
+        mgr = writer.manager
+        self.writer, self.seg_bytes = writer, seg_bytes
+        self.table, self.table_addr = mgr.alloc_table(
+            len(seg_bytes), writer.handle.shuffle_id)
+        self.blocks = []
+        self.dst = np.zeros(nd, dtype=np.int64)
+        self.spilled = []   # (parts, total) that did not fit the HBM pool
+        meta_key = make_key(mgr.executor_id, 1)
+        for parts in group_partitions(seg_bytes,
+                                      mgr.conf.shuffle_write_block_size):
+            total = int(sum(seg_bytes[p] for p in parts))
+            if total == 0:
+                for p in parts:
+                    self.table.put(p, 0, 0, meta_key)
+                continue
+            try:
+                blk = mgr.gpu.pool.get(total)
+            except MemoryError:
+                self.spilled.append((parts, total))
+                continue
+            self._put(parts, blk.offset,
+                      make_key(mgr.executor_id, blk.segment_id),
+                      mgr.gpu.local_base(blk.segment_id))
+            self.blocks.append(blk)
+        self.stage = torch.empty(sum(t for _, t in self.spilled),
+                                 dtype=torch.uint8, device=device)
+        addr = self.stage.data_ptr()
+        for parts, _total in self.spilled:
+            for p in parts:
+                if seg_bytes[p]:
+                    self.dst[p] = addr
+                addr += int(seg_bytes[p])
+
+    def _put(self, parts, off: int, key: int, base: Optional[int] = None):
+        """Table entries of one placed group, back to back from offset
+        ``off`` of its segment; for an HBM block ``base``, the slab's
+        device address, also sets ``dst``."""
+        for p in parts:
+            nb = int(self.seg_bytes[p])
+            self.table.put(p, off, nb, key)
+            if nb and base is not None:
+                self.dst[p] = base + off
+            off += nb
+            self.writer.metrics.bytes_written += nb
+
+    def finish(self, records: int) -> None:
+        """After the kernel is queued: wait for it, move the spilled groups
+        to host blocks, publish."""
+        import torch
+        w = self.writer
+        mgr = w.manager
+        torch.cuda.synchronize()
+        soff = 0
+        for parts, total in self.spilled:
+            hblk = mgr.pool.get(total)     # host pool
+            mgr.data_segment(hblk.segment_id).write(
+                hblk.offset,
+                self.stage[soff:soff + total].cpu().numpy().tobytes())
+            self._put(parts, hblk.offset,
+                      make_key(mgr.executor_id, hblk.segment_id))
+            soff += total
+            self.blocks.append(hblk)
+        w.metrics.records_written += records
+        mgr.keep_alive(w.handle, w.map_id, self.blocks)
+        mgr.publish_map_output(w.handle, w.map_id, self.table_addr)
+
+
 class ShuffleWriter:
     """One map task's writer: accumulate → partition → lay out → publish."""
 
@@ -76,6 +180,9 @@ class ShuffleWriter:
         self._key_batches: List[np.ndarray] = []
         self._value_batches: List[Optional[np.ndarray]] = []
         self._byte_records: Optional[List[List[bytes]]] = None
+        self._gpu_batches: list = []      # (keys, values) device tensors
+        self._gpu_records: list = []      # flat uint8 device tensors
+        self._record_shape: Optional[tuple] = None  # (record, key) bytes
         self._stopped = False
 
     # -- fixed-width tensor path ---------------------------------------
@@ -92,7 +199,6 @@ class ShuffleWriter:
     def write_device_batch(self, keys, values=None) -> None:
         """keys/values: int64 CUDA tensors. Partitioned and serialized by
         the radix kernel straight into HBM pool blocks at stop()."""
-        self._gpu_batches = getattr(self, "_gpu_batches", [])
         self._gpu_batches.append((keys, values))
 
     def write_device_records(self, records, record_bytes: int,
@@ -108,10 +214,9 @@ class ShuffleWriter:
             raise ValueError("record_bytes must be a multiple of 4, >= 8")
         if key_bytes not in (8, 10):
             raise ValueError("key_bytes must be 8 or 10")
-        self._gpu_records = getattr(self, "_gpu_records", [])
         if records.numel() % record_bytes:
             raise ValueError("records length not a record multiple")
-        prev = getattr(self, "_record_shape", None)
+        prev = self._record_shape
         if prev is not None and prev != (record_bytes, key_bytes):
             raise ValueError("record shape changed between batches")
         self._record_shape = (record_bytes, key_bytes)
@@ -182,9 +287,9 @@ class ShuffleWriter:
         if not success:
             return
         t0 = time.perf_counter_ns()
-        if getattr(self, "_gpu_records", None):
+        if self._gpu_records:
             self._commit_gpu_records(partitioner)
-        elif getattr(self, "_gpu_batches", None):
+        elif self._gpu_batches:
             self._commit_gpu(partitioner, combiner, combine_key_bits)
         else:
             if self._byte_records is not None:
@@ -205,13 +310,13 @@ class ShuffleWriter:
         check_aggregator(combiner, "combiner")
         if not 1 <= combine_key_bits <= 64:
             raise ValueError("combine_key_bits must be in [1, 64]")
-        if getattr(self, "_gpu_records", None):
+        if self._gpu_records:
             raise ValueError("map-side combine does not cover wide records "
                              "(write_device_records)")
         if self._byte_records is not None:
             raise ValueError("map-side combine does not cover the pickled "
                              "lane (write_records)")
-        for _k, v in getattr(self, "_gpu_batches", None) or []:
+        for _k, v in self._gpu_batches:
             if v is None:
                 raise ValueError("map-side combine needs values; a "
                                  "value-less batch was written")
@@ -296,8 +401,8 @@ class ShuffleWriter:
         CPU writer + mmap + register, RdmaMappedFile.java:113-189)."""
         import torch
         from .ops import load as ops_load
-        mgr = self.manager
-        if mgr.gpu is None:
+        from .ops.radix import digit_counts
+        if self.manager.gpu is None:
             raise RuntimeError("GPU writer requires the GPU data plane")
         hs = ops_load()
         R = self.handle.num_partitions
@@ -349,201 +454,73 @@ class ShuffleWriter:
             self._commit_empty()
             return
         dev = keys.device
-        stream = torch.cuda.current_stream().cuda_stream
-        nd = 1 << nbits_eff
-        hist = torch.empty(hs.radix_hist_bytes(n, nbits_eff) // 4,
-                           dtype=torch.int32, device=dev)
-        scan_ws = torch.empty(hs.radix_scan_ws_bytes(n, nbits_eff) // 4,
-                              dtype=torch.int32, device=dev)
-        totals = torch.empty(nd, dtype=torch.int32, device=dev)
-        hs.radix_hist(keys.data_ptr(), n, shift, nbits_eff, hist.data_ptr(),
-                      stream, func, 1, nparts)
-        hs.radix_scan(hist.data_ptr(), n, nbits_eff, totals.data_ptr(),
-                      scan_ws.data_ptr(), stream)
+        hist, totals = digit_counts(keys.data_ptr(), n, shift, nbits_eff, dev,
+                                    func, 1, nparts)
         counts = totals.cpu().numpy().astype(np.int64)[:R]  # syncs the stream
-        rec_w = HEADER_W + (8 if has_val else 0)
-        seg_bytes = counts * rec_w
-
-        # greedy chunking of partitions into HBM blocks (same policy as host)
-        table, table_addr = mgr.alloc_table(R, self.handle.shuffle_id)
-        write_block = mgr.conf.shuffle_write_block_size
-        pool = mgr.gpu.pool
-        blocks = []
-        key_dst = np.zeros(nd, dtype=np.int64)
-        val_dst = np.zeros(nd, dtype=np.int64)
-        group, group_bytes = [], 0
-        flushes = []
-        for p in range(R):
-            if group and group_bytes + seg_bytes[p] > write_block:
-                flushes.append(group)
-                group, group_bytes = [], 0
-            group.append(p)
-            group_bytes += int(seg_bytes[p])
-        if group:
-            flushes.append(group)
-        meta_key = make_key(mgr.executor_id, 1)
-        spill_groups = []   # (parts, total) that did not fit the HBM pool
-        for parts in flushes:
-            total = int(sum(seg_bytes[p] for p in parts))
-            if total == 0:
-                for p in parts:
-                    table.put(p, 0, 0, meta_key)
-                continue
-            try:
-                blk = pool.get(total)
-            except MemoryError:
-                # pool pressure: this group spills to a host block after
-                # the scatter (reference keeps a disk file path for
-                # overflow — SURVEY §7.1 RdmaMappedFile row)
-                spill_groups.append((parts, total))
-                continue
-            base = mgr.gpu.local_base(blk.segment_id)
-            key = make_key(mgr.executor_id, blk.segment_id)
-            off = blk.offset
-            for p in parts:
-                nb = int(seg_bytes[p])
-                table.put(p, off, nb, key)
-                if nb:
-                    # AoS segment: record r's key at +r*16, value at +r*16+8
-                    key_dst[p] = base + off
-                    val_dst[p] = base + off + (8 if has_val else 0)
-                off += nb
-                self.metrics.bytes_written += nb
-            blocks.append(blk)
-        spill_stage = None
-        if spill_groups:
-            # scatter spilled partitions into one transient device staging
-            # tensor, then copy each group to a pooled host block
-            stage_total = sum(t for _, t in spill_groups)
-            spill_stage = torch.empty(stage_total, dtype=torch.uint8,
-                                      device=dev)
-            soff = 0
-            for parts, total in spill_groups:
-                for p in parts:
-                    nb = int(seg_bytes[p])
-                    if nb:
-                        key_dst[p] = spill_stage.data_ptr() + soff
-                        val_dst[p] = spill_stage.data_ptr() + soff + \
-                            (8 if has_val else 0)
-                    # table filled after host placement below
-                    soff += nb
-        kd = torch.from_numpy(key_dst).to(dev)
-        vd = torch.from_numpy(val_dst).to(dev)
+        layout = _GpuLayout(self, counts * (16 if has_val else HEADER_W),
+                            1 << nbits_eff, dev)
+        # AoS segment: record r's key at +r*16, value at +r*16+8
+        kd = torch.from_numpy(layout.dst).to(dev)
+        vd = (torch.from_numpy(np.where(layout.dst != 0, layout.dst + 8, 0))
+              .to(dev) if has_val else kd)
         hs.radix_scatter(keys.data_ptr(),
                          vals.data_ptr() if has_val else 0,
                          n, shift, nbits_eff, hist.data_ptr(),
-                         kd.data_ptr(), vd.data_ptr(), stream, func,
+                         kd.data_ptr(), vd.data_ptr(),
+                         torch.cuda.current_stream().cuda_stream, func,
                          1 if has_val else 0, 1, nparts)
-        torch.cuda.synchronize()
-        if spill_groups:
-            soff = 0
-            for parts, total in spill_groups:
-                hblk = mgr.pool.get(total)     # host pool
-                hseg = mgr.data_segment(hblk.segment_id)
-                hkey = make_key(mgr.executor_id, hblk.segment_id)
-                cpu_bytes = spill_stage[soff:soff + total].cpu().numpy()
-                hseg.write(hblk.offset, cpu_bytes.tobytes())
-                off = hblk.offset
-                for p in parts:
-                    nb = int(seg_bytes[p])
-                    table.put(p, off, nb, hkey)
-                    off += nb
-                    self.metrics.bytes_written += nb
-                soff += total
-                blocks.append(hblk)
-        self.metrics.records_written += n
-        mgr.keep_alive(self.handle, self.map_id, blocks)
-        mgr.publish_map_output(self.handle, self.map_id, table_addr)
+        layout.finish(n)
 
-    def _group_pairs_2level(self, hs, recs, n, W, key_bytes, R,
-                            func, shift, nparts, dev, stream, bounds=None):
+    def _group_pairs_2level(self, recs, n, W, key_bytes, R,
+                            func, shift, nparts, bounds=None):
         """> 4096 partitions: the single radix pass is capped at 2^12 LDS
         digits, so the PARTITION ID itself is radixed in two levels —
         extract (pid, aux) pairs, scatter by pid>>12 (coarse), then per
-        coarse bucket by pid&4095 (fine). Returns (full R counts, pairs,
-        grouped pairs, gather digit params: pid is pair.x so the gather
-        recomputes it as plain bits). ``bounds`` (device split points,
-        func 4) selects the splitter-search extract."""
+        coarse bucket by pid&4095 (fine). Returns (full R counts, grouped
+        pairs, pid mask): pid is pair.x, so the gather recomputes it as
+        plain bits under that mask (func 0, shift 0)."""
         import torch
-        nbits = (R - 1).bit_length()
-        if nbits > 24:
-            raise ValueError(f"GPU partitioner supports R <= 2^24, got {R}")
-        mask_full = (1 << nbits) - 1
+        from .ops.radix import digit_counts, extract_pairs, scatter_pairs
+        dev = recs.device
+        mask_full = (1 << (R - 1).bit_length()) - 1   # R <= 2^24
         G = (R + 4095) >> 12
         nbits_c = max((G - 1).bit_length(), 4)
-        ndc = 1 << nbits_c
-        pairs = torch.empty(2 * n, dtype=torch.int64, device=dev)
-        if bounds is not None:
-            hs.extract_pairs_bounds(recs.data_ptr(), n, W, key_bytes,
-                                    pairs.data_ptr(), bounds.data_ptr(),
-                                    bounds.numel(), stream)
-        else:
-            hs.extract_pairs(recs.data_ptr(), n, W, key_bytes,
-                             pairs.data_ptr(), stream, func, shift,
-                             mask_full, nparts)
-        hist = torch.empty(hs.radix_hist_bytes(n, 12) // 4,
-                           dtype=torch.int32, device=dev)
-        scan_ws = torch.empty(hs.radix_scan_ws_bytes(n, 12) // 4,
-                              dtype=torch.int32, device=dev)
-        totals_c = torch.empty(ndc, dtype=torch.int32, device=dev)
+        pairs = extract_pairs(recs, W, key_bytes, bounds=bounds,
+                              pid=(func, shift, mask_full, nparts))
         # coarse: group by pid >> 12
-        hs.radix_hist(pairs.data_ptr(), n, 12, nbits_c, hist.data_ptr(),
-                      stream, 0, 2, 0)
-        hs.radix_scan(hist.data_ptr(), n, nbits_c, totals_c.data_ptr(),
-                      scan_ws.data_ptr(), stream)
+        hist, totals_c = digit_counts(pairs.data_ptr(), n, 12, nbits_c, dev,
+                                      0, 2)
         counts_c = totals_c.cpu().numpy().astype(np.int64)[:G]   # sync
-        starts_c = np.zeros(G, dtype=np.int64)
-        np.cumsum(counts_c[:-1], out=starts_c[1:])
+        starts_c = np.cumsum(counts_c) - counts_c
         pairs_c = torch.empty_like(pairs)
         bases_c = torch.from_numpy(
-            np.pad(starts_c, (0, ndc - G))).to(dev)
-        kd = pairs_c.data_ptr() + bases_c * 16
-        vd = kd + 8
-        hs.radix_scatter(pairs.data_ptr(), pairs.data_ptr() + 8, n, 12,
-                         nbits_c, hist.data_ptr(), kd.data_ptr(),
-                         vd.data_ptr(), stream, 0, 1, 2, 0)
+            np.pad(starts_c, (0, (1 << nbits_c) - G))).to(dev)
+        scatter_pairs(pairs, n, 12, nbits_c, hist,
+                      pairs_c.data_ptr() + bases_c * 16)
         # fine: per coarse bucket, group its subrange by pid & 4095.
         # All fine hists run first (stream-ordered, per-bucket totals
         # persist), ONE sync, then all fine scatters.
-        totals_f = torch.empty(G * 4096, dtype=torch.int32, device=dev)
-        bhists = []
+        totals_f = torch.zeros(G * 4096, dtype=torch.int32, device=dev)
+        fine = []
         for b in range(G):
             cnt = int(counts_c[b])
             if cnt == 0:
-                totals_f[b * 4096:(b + 1) * 4096] = 0
-                bhists.append(None)
                 continue
-            bh = torch.empty(hs.radix_hist_bytes(cnt, 12) // 4,
-                             dtype=torch.int32, device=dev)
-            bws = torch.empty(hs.radix_scan_ws_bytes(cnt, 12) // 4,
-                              dtype=torch.int32, device=dev)
-            sub = pairs_c.data_ptr() + starts_c[b] * 16
-            hs.radix_hist(sub, cnt, 0, 12, bh.data_ptr(), stream, 0, 2, 0)
-            hs.radix_scan(bh.data_ptr(), cnt, 12,
-                          totals_f.data_ptr() + b * 4096 * 4,
-                          bws.data_ptr(), stream)
-            bhists.append((bh, bws, sub, cnt))
+            sub = pairs_c[2 * starts_c[b]:2 * (starts_c[b] + cnt)]
+            span = slice(b * 4096, (b + 1) * 4096)
+            bh, _ = digit_counts(sub.data_ptr(), cnt, 0, 12, dev, 0, 2,
+                                 totals=totals_f[span])
+            fine.append((bh, sub, cnt, span))   # bh lives on to the scatter
         counts_full = totals_f.cpu().numpy().astype(np.int64)[:R]   # sync
         # pids b*4096+j with j beyond R's tail never occur; length R slice
-        starts_full = np.zeros(R, dtype=np.int64)
-        np.cumsum(counts_full[:-1], out=starts_full[1:])
+        starts_full = np.cumsum(counts_full) - counts_full
         pairs_f = pairs   # reuse: original extraction no longer needed
-        base_addr = pairs_f.data_ptr() + torch.from_numpy(
-            starts_full).to(dev) * 16
-        for b in range(G):
-            if bhists[b] is None:
-                continue
-            bh, bws, sub, cnt = bhists[b]
-            lo = b * 4096
-            hi = min(lo + 4096, R)
-            kd_b = torch.zeros(4096, dtype=torch.int64, device=dev)
-            kd_b[:hi - lo] = base_addr[lo:hi]
-            vd_b = kd_b + 8
-            hs.radix_scatter(sub, sub + 8, cnt, 0, 12, bh.data_ptr(),
-                             kd_b.data_ptr(), vd_b.data_ptr(), stream,
-                             0, 1, 2, 0)
-        # gather digit = pair.x (the pid) verbatim: func 0, shift 0
-        return counts_full, pairs_c, pairs_f, 0, 0, mask_full, 0
+        base_addr = torch.from_numpy(np.pad(
+            pairs_f.data_ptr() + starts_full * 16,
+            (0, G * 4096 - R))).to(dev)
+        for bh, sub, cnt, span in fine:
+            scatter_pairs(sub, cnt, 0, 12, bh, base_addr[span])
+        return counts_full, pairs_f, mask_full
 
     def _commit_gpu_records(self, partitioner) -> None:
         """Wide-record map-side GPU write. Records stay put while 16-byte
@@ -553,11 +530,10 @@ class ShuffleWriter:
         reference's CPU writer + mmap + register for arbitrary-width
         records (RdmaMappedFile.java:113-189)."""
         import torch
-        from .ops import load as ops_load
-        mgr = self.manager
-        if mgr.gpu is None:
+        from .ops.radix import (digit_counts, extract_pairs, gather_grouped,
+                                group_records)
+        if self.manager.gpu is None:
             raise RuntimeError("GPU writer requires the GPU data plane")
-        hs = ops_load()
         R = self.handle.num_partitions
         func, shift, nparts, nbits_eff = self._gpu_part_params(partitioner)
         W, key_bytes = self._record_shape
@@ -568,8 +544,6 @@ class ShuffleWriter:
             self._commit_empty()
             return
         dev = recs.device
-        stream = torch.cuda.current_stream().cuda_stream
-        two_level = (R - 1).bit_length() > 12
         # split-point partitioner: the extract searches the bounds and
         # leaves the partition id in pair.x
         bounds = (partitioner.gpu_bounds(dev) if func == PART_BOUNDS
@@ -579,132 +553,24 @@ class ShuffleWriter:
             raise ValueError(
                 f"partitioner has {bounds.numel()} split points, the "
                 f"shuffle was registered with {R} partitions")
-        if two_level:
-            counts_nd, pairs, pairs_out, gfunc, gshift, gmask, gnparts = \
-                self._group_pairs_2level(hs, recs, n, W, key_bytes, R,
-                                         func, shift, nparts, dev, stream,
-                                         bounds)
-            nd = R
+        if (R - 1).bit_length() > 12:
+            # the pairs are grouped while the counts are discovered
+            counts, grouped, mask = self._group_pairs_2level(
+                recs, n, W, key_bytes, R, func, shift, nparts, bounds)
+            layout = _GpuLayout(self, counts * W, R, dev)
+            gather_grouped(recs, grouped, n, W, counts, layout.dst, 0, mask)
         else:
-            nd = 1 << nbits_eff
-            pairs = torch.empty(2 * n, dtype=torch.int64, device=dev)
+            pairs = extract_pairs(recs, W, key_bytes, bounds=bounds)
             if bounds is not None:
-                hs.extract_pairs_bounds(recs.data_ptr(), n, W, key_bytes,
-                                        pairs.data_ptr(), bounds.data_ptr(),
-                                        bounds.numel(), stream)
                 # hist / scatter / gather read the pid as plain bits
                 func, shift, nparts = 0, 0, 0
-            else:
-                hs.extract_pairs(recs.data_ptr(), n, W, key_bytes,
-                                 pairs.data_ptr(), stream)
-            gfunc, gshift, gmask, gnparts = func, shift, nd - 1, nparts
-            hist = torch.empty(hs.radix_hist_bytes(n, nbits_eff) // 4,
-                               dtype=torch.int32, device=dev)
-            scan_ws = torch.empty(hs.radix_scan_ws_bytes(n, nbits_eff) // 4,
-                                  dtype=torch.int32, device=dev)
-            totals = torch.empty(nd, dtype=torch.int32, device=dev)
-            hs.radix_hist(pairs.data_ptr(), n, shift, nbits_eff,
-                          hist.data_ptr(), stream, func, 2, nparts)
-            hs.radix_scan(hist.data_ptr(), n, nbits_eff, totals.data_ptr(),
-                          scan_ws.data_ptr(), stream)
-            counts_nd = totals.cpu().numpy().astype(np.int64)  # syncs
-            pairs_out = None   # grouped below, after the layout
-        counts = counts_nd[:R]
-        seg_bytes = counts * W
-
-        # greedy chunking of partitions into HBM blocks (same policy as
-        # the 16-byte path / RdmaMappedFile.java:113-157)
-        table, table_addr = mgr.alloc_table(R, self.handle.shuffle_id)
-        write_block = mgr.conf.shuffle_write_block_size
-        pool = mgr.gpu.pool
-        blocks = []
-        rec_dst = np.zeros(nd, dtype=np.int64)    # byte base per digit
-        group, group_bytes = [], 0
-        flushes = []
-        for p in range(R):
-            if group and group_bytes + seg_bytes[p] > write_block:
-                flushes.append(group)
-                group, group_bytes = [], 0
-            group.append(p)
-            group_bytes += int(seg_bytes[p])
-        if group:
-            flushes.append(group)
-        meta_key = make_key(mgr.executor_id, 1)
-        spill_groups = []   # (parts, total) that did not fit the HBM pool
-        for parts in flushes:
-            total = int(sum(seg_bytes[p] for p in parts))
-            if total == 0:
-                for p in parts:
-                    table.put(p, 0, 0, meta_key)
-                continue
-            try:
-                blk = pool.get(total)
-            except MemoryError:
-                spill_groups.append((parts, total))
-                continue
-            base = mgr.gpu.local_base(blk.segment_id)
-            key = make_key(mgr.executor_id, blk.segment_id)
-            off = blk.offset
-            for p in parts:
-                nb = int(seg_bytes[p])
-                table.put(p, off, nb, key)
-                if nb:
-                    rec_dst[p] = base + off
-                off += nb
-                self.metrics.bytes_written += nb
-            blocks.append(blk)
-        spill_stage = None
-        if spill_groups:
-            stage_total = sum(t for _, t in spill_groups)
-            spill_stage = torch.empty(stage_total, dtype=torch.uint8,
-                                      device=dev)
-            soff = 0
-            for parts, total in spill_groups:
-                for p in parts:
-                    nb = int(seg_bytes[p])
-                    if nb:
-                        rec_dst[p] = spill_stage.data_ptr() + soff
-                    soff += nb
-
-        # group the PAIRS by digit (contiguous per-digit runs)
-        starts = np.zeros(nd, dtype=np.int64)
-        np.cumsum(counts_nd[:-1], out=starts[1:])
-        if pairs_out is None:   # single-pass grouping (two-level grouped
-            pairs_out = torch.empty_like(pairs)    # during count discovery)
-            bases_t = torch.from_numpy(starts).to(dev)
-            kd = pairs_out.data_ptr() + bases_t * 16
-            vd = kd + 8
-            hs.radix_scatter(pairs.data_ptr(), pairs.data_ptr() + 8, n,
-                             shift, nbits_eff, hist.data_ptr(),
-                             kd.data_ptr(), vd.data_ptr(), stream, func, 1,
-                             2, nparts)
-        # one gather moves every record to its final slot
-        dstart_t = torch.from_numpy(starts.astype(np.uint32)
-                                    .view(np.int32)).to(dev)
-        dst_addr_t = torch.from_numpy(rec_dst).to(dev)
-        hs.gather_records(recs.data_ptr(), pairs_out.data_ptr(), n, W, 1, 0,
-                          dst_addr_t.data_ptr(), dstart_t.data_ptr(), gshift,
-                          gmask, gfunc, gnparts, stream)
-        torch.cuda.synchronize()
-        if spill_groups:
-            soff = 0
-            for parts, total in spill_groups:
-                hblk = mgr.pool.get(total)     # host pool
-                hseg = mgr.data_segment(hblk.segment_id)
-                hkey = make_key(mgr.executor_id, hblk.segment_id)
-                cpu_bytes = spill_stage[soff:soff + total].cpu().numpy()
-                hseg.write(hblk.offset, cpu_bytes.tobytes())
-                off = hblk.offset
-                for p in parts:
-                    nb = int(seg_bytes[p])
-                    table.put(p, off, nb, hkey)
-                    off += nb
-                    self.metrics.bytes_written += nb
-                soff += total
-                blocks.append(hblk)
-        self.metrics.records_written += n
-        mgr.keep_alive(self.handle, self.map_id, blocks)
-        mgr.publish_map_output(self.handle, self.map_id, table_addr)
+            hist, totals = digit_counts(pairs.data_ptr(), n, shift,
+                                        nbits_eff, dev, func, 2, nparts)
+            counts = totals.cpu().numpy().astype(np.int64)  # syncs
+            layout = _GpuLayout(self, counts[:R] * W, 1 << nbits_eff, dev)
+            group_records(recs, W, pairs, n, shift, nbits_eff, hist, counts,
+                          layout.dst, func, nparts)
+        layout.finish(n)
 
     def _commit_empty(self) -> None:
         """Zero-record map task: publish an all-empty location table."""
@@ -724,20 +590,9 @@ class ShuffleWriter:
         table, table_addr = mgr.alloc_table(self.handle.num_partitions,
                                     self.handle.shuffle_id)
         blocks = []
-        # greedy grouping of partitions into blocks
-        group: List[int] = []
-        group_bytes = 0
-        flushes: List[List[int]] = []
-        for p, seg in enumerate(segments):
-            if group and group_bytes + len(seg) > write_block:
-                flushes.append(group)
-                group, group_bytes = [], 0
-            group.append(p)
-            group_bytes += len(seg)
-        if group:
-            flushes.append(group)
         meta_key = make_key(mgr.executor_id, 1)  # META_SEGMENT_ID
-        for parts in flushes:
+        for parts in group_partitions([len(seg) for seg in segments],
+                                      write_block):
             total = sum(len(segments[p]) for p in parts)
             if total == 0:
                 for p in parts:
