@@ -24,7 +24,7 @@ def ext_path() -> str:
 def sources():
     return [os.path.join(CSRC, f) for f in ("pool.cpp", "kernels.hip",
                                             "reduce.hip", "bounds.hip",
-                                            "bindings.cpp")]
+                                            "join.hip", "bindings.cpp")]
 
 
 def needs_build() -> bool:

@@ -153,4 +153,16 @@ PYBIND11_MODULE(_hipshuffle, m) {
   m.def("reduce_by_key_emit", &hs::reduce_by_key_emit, py::arg("pairs"),
         py::arg("n"), py::arg("op"), py::arg("ws"), py::arg("out_keys"),
         py::arg("out_vals"), py::arg("stream") = 0);
+  m.def("join_expand_tile", &hs::join_expand_tile);
+  m.def("join_expand_lds_rows", &hs::join_expand_lds_rows);
+  m.def("join_probe_lds_keys", &hs::join_probe_lds_keys);
+  m.def("join_probe", &hs::join_probe, py::arg("p_keys"), py::arg("np"),
+        py::arg("q_keys"), py::arg("nq"), py::arg("lo"), py::arg("m"),
+        py::arg("stream") = 0);
+  m.def("join_expand", &hs::join_expand, py::arg("p_keys"),
+        py::arg("p_vals"), py::arg("q_vals"), py::arg("lo"), py::arg("m"),
+        py::arg("offsets"), py::arg("np"), py::arg("total"),
+        py::arg("out_key"), py::arg("out_p_val"), py::arg("out_q_val"),
+        py::arg("out_q_valid"), py::arg("out_p_idx"), py::arg("out_q_idx"),
+        py::arg("stream") = 0);
 }

@@ -151,4 +151,25 @@ void extract_pairs_bounds(uintptr_t recs, uint64_t n, uint32_t rec_bytes,
                           uintptr_t bounds, uint32_t nbounds,
                           uintptr_t stream, uint64_t idx_base = 0);
 
+// join.hip — sort-merge join family over key-sorted SoA tables; P probes Q,
+// keys compare as unsigned 64-bit, np and nq < 2^31.
+// join_probe: lo[i] = lower_bound(Q, pkey[i]), m[i] = matches of row i (u32).
+// join_expand: output row o belongs to the last P row i with
+// offsets[i] <= o (offsets: exclusive u64 scan of the per-row output
+// counts, total: their sum) and is its match j = o - offsets[i]. Every
+// out_* may be 0 (skipped): out_key / out_p_val / out_p_idx take pkey[i],
+// pval[i], i; out_q_val / out_q_valid (u8) / out_q_idx (i64) take
+// qval[lo[i] + j], 1, lo[i] + j where m[i] != 0 and 0, 0, -1 elsewhere.
+int join_expand_tile();
+int join_expand_lds_rows();
+int join_probe_lds_keys();
+void join_probe(uintptr_t p_keys, uint32_t np, uintptr_t q_keys, uint32_t nq,
+                uintptr_t lo, uintptr_t m, uintptr_t stream);
+void join_expand(uintptr_t p_keys, uintptr_t p_vals, uintptr_t q_vals,
+                 uintptr_t lo, uintptr_t m, uintptr_t offsets, uint32_t np,
+                 uint64_t total, uintptr_t out_key, uintptr_t out_p_val,
+                 uintptr_t out_q_val, uintptr_t out_q_valid,
+                 uintptr_t out_p_idx, uintptr_t out_q_idx,
+                 uintptr_t stream);
+
 }  // namespace hipshuffle
