@@ -131,7 +131,32 @@ def main():
         print(f"sampled bounds: keys per partition = {sizes} "
               f"(uniform bounds: {uni.tolist()})")
 
-        # 6) metrics: the task/executor counters the reference feeds Spark
+        # 6) variable-length rows: u64 key + a payload of any length ------
+        # CSR layout (keys, offsets, data): row r is
+        # data[offsets[r]:offsets[r + 1]]. write_varlen is the CPU lane;
+        # write_device_varlen takes the same three as CUDA tensors.
+        words = [f"value-{i}".encode() * (i % 4) for i in range(1000)]
+        k = rng.integers(0, 20, len(words), dtype=np.uint64)
+        offsets = np.concatenate([[0], np.cumsum([len(w) for w in words])])
+        handle = eng.register_shuffle(num_maps=1, num_partitions=4)
+        writer = mgr.get_writer(handle, map_id=0)
+        writer.write_varlen(k, offsets, np.frombuffer(b"".join(words),
+                                                      dtype=np.uint8))
+        writer.stop(True, partitioner=HashPartitioner(4))
+        gk, goff, gdata = mgr.get_reader(handle, 0, 3).read_varlen(
+            ordering=True)                 # grouped: equal keys adjacent
+        if hasattr(gk, "cpu"):             # GPU data plane: device tensors
+            gk, goff, gdata = (t.cpu().numpy() for t in (gk, goff, gdata))
+        buf = gdata.tobytes()
+        assert sorted(buf[goff[r]:goff[r + 1]] for r in range(len(gk))) \
+            == sorted(words)
+        gk = gk.view(np.uint64)
+        assert np.all(gk[1:] >= gk[:-1])
+        eng.unregister_shuffle(handle)
+        print(f"variable-length: {len(gk)} rows, {len(buf)} payload bytes, "
+              f"{len(np.unique(gk))} groups")
+
+        # 7) metrics: the task/executor counters the reference feeds Spark
         print("lifetime:", mgr.lifetime_metrics.format())
 
 

@@ -24,7 +24,8 @@ def ext_path() -> str:
 def sources():
     return [os.path.join(CSRC, f) for f in ("pool.cpp", "kernels.hip",
                                             "reduce.hip", "bounds.hip",
-                                            "join.hip", "bindings.cpp")]
+                                            "join.hip", "varlen.hip",
+                                            "bindings.cpp")]
 
 
 def needs_build() -> bool:

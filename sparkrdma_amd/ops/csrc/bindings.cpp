@@ -165,4 +165,10 @@ PYBIND11_MODULE(_hipshuffle, m) {
         py::arg("out_key"), py::arg("out_p_val"), py::arg("out_q_val"),
         py::arg("out_q_valid"), py::arg("out_p_idx"), py::arg("out_q_idx"),
         py::arg("stream") = 0);
+  m.def("varlen_copy_tile_bytes", &hs::varlen_copy_tile_bytes);
+  m.def("varlen_copy_lds_rows", &hs::varlen_copy_lds_rows);
+  m.def("varlen_copy", &hs::varlen_copy, py::arg("cum"), py::arg("src"),
+        py::arg("n"), py::arg("seg_off"), py::arg("seg_dst"),
+        py::arg("nseg"), py::arg("total"), py::arg("stream") = 0,
+        py::arg("wide_loads") = 1);
 }

@@ -172,4 +172,19 @@ void join_expand(uintptr_t p_keys, uintptr_t p_vals, uintptr_t q_vals,
                  uintptr_t out_p_idx, uintptr_t out_q_idx,
                  uintptr_t stream);
 
+// varlen.hip — byte-granular copy of n rows of different lengths, balanced
+// by destination bytes. cum: u64[n + 1] exclusive scan of the row lengths in
+// destination order (cum[0] == 0, cum[n] == total); src: u64[n] byte address
+// of every row; the destination is nseg contiguous ranges: range s takes the
+// virtual bytes [seg_off[s], seg_off[s + 1]) (u64[nseg + 1], seg_off[0] == 0,
+// seg_off[nseg] == total) at byte address seg_dst[s] (u64[nseg]). Any source
+// and destination alignment; no byte outside a range is written.
+// n, nseg < 2^31. wide_loads == 0 reads every source byte with a byte load
+// (the measured alternative, scripts/bench_varlen.py).
+int varlen_copy_tile_bytes();
+int varlen_copy_lds_rows();
+void varlen_copy(uintptr_t cum, uintptr_t src, uint64_t n, uintptr_t seg_off,
+                 uintptr_t seg_dst, uint64_t nseg, uint64_t total,
+                 uintptr_t stream, int wide_loads = 1);
+
 }  // namespace hipshuffle

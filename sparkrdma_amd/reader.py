@@ -751,6 +751,7 @@ class ShuffleReader:
         self.handle = handle
         self.start_partition = start_partition
         self.end_partition = end_partition
+        self._fixed_records = records is not None or bool(in_place)
         self.fetcher = FetcherIterator(manager, handle,
                                        start_partition, end_partition,
                                        arena=arena, records=records,
@@ -902,6 +903,111 @@ class ShuffleReader:
             end = len(bio.getvalue())
             while bio.tell() < end:
                 yield pickle.load(bio)
+
+    # ---------------- variable-length rows (varlen.py) -----------------
+
+    def read_varlen(self, ordering: bool = False, end_bit: int = 64):
+        """Consume the whole partition range of variable-length rows
+        (``write_varlen`` / ``write_device_varlen``). Returns ``(keys,
+        offsets, data)`` in the CSR layout the writer took: ``keys`` has n
+        entries, ``offsets`` is int64[n + 1] with ``offsets[0] == 0`` and
+        row r is ``data[offsets[r]:offsets[r + 1]]`` (uint8). An empty
+        range gives n = 0 and ``offsets == [0]``.
+
+        With the GPU data plane the three are device tensors (keys int64
+        holding u64 bits) and the payloads are moved by the byte-balanced
+        copy of ops/csrc/varlen.hip; without it they are numpy arrays.
+        ``ordering=True`` sorts the rows by key bits [0, end_bit)
+        (unsigned); the order among equal keys is unspecified. Not
+        available on a reader opened with ``records=`` or
+        ``in_place=True``: those describe fixed-width records."""
+        if self._fixed_records:
+            raise ValueError("read_varlen is not available on a reader "
+                             "opened with records= or in_place=True")
+        if not 1 <= end_bit <= 64:
+            raise ValueError("end_bit must be in [1, 64]")
+        if self.manager.gpu is not None:
+            return self._read_varlen_gpu(ordering, end_bit)
+        import numpy as np
+        from .varlen import concat_rows, take_rows, unpack_varlen_segment
+        keys, offsets, data = concat_rows(
+            [unpack_varlen_segment(bytes(blk)) for _ref, blk in self.fetcher])
+        if ordering and len(keys):
+            mask = np.uint64((1 << end_bit) - 1) if end_bit < 64 \
+                else np.uint64(2 ** 64 - 1)
+            order = np.argsort(keys & mask, kind="stable")
+            keys = keys[order]
+            offsets, data = take_rows(offsets, data, order)
+        return keys, offsets, data
+
+    def _read_varlen_gpu(self, ordering: bool, end_bit: int):
+        """Drain into the arena, read every block's header with one D2H
+        copy, then two byte-balanced copies: the blocks' index sections
+        into one (key, end) table, and — after the optional sort of (key,
+        row id) pairs — the payloads into one contiguous heap."""
+        import numpy as np
+        import torch
+        from .ops.varlen import exclusive_scan, varlen_copy
+        from .varlen import (HEADER_BYTES, INDEX_ENTRY_BYTES, segment_bytes)
+        dev = torch.device("cuda", self.manager.gpu.device)
+        blocks = [blk for _ref, blk in self.fetcher if len(blk)]
+        for blk in blocks:
+            if len(blk) % 16 or blk.data_ptr() % 16:
+                raise ValueError("a fetched block is not a 16-byte aligned "
+                                 "variable-length segment")
+
+        def i64(a):
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)) \
+                .to(dev)
+
+        S = len(blocks)
+        head = (torch.cat([b[:HEADER_BYTES] for b in blocks])
+                .view(torch.int64).cpu().numpy().reshape(S, 2)
+                if S else np.zeros((0, 2), dtype=np.int64))   # THE sync
+        nb, hb = head[:, 0], head[:, 1]
+        for b, blk in enumerate(blocks):
+            if nb[b] <= 0 or hb[b] < 0 \
+                    or segment_bytes(int(nb[b]), int(hb[b])) != len(blk):
+                raise ValueError(
+                    f"block header (n={nb[b]}, H={hb[b]}) does not match "
+                    f"its length {len(blk)}: not a variable-length segment")
+        n, heap = int(nb.sum()), int(hb.sum())
+        if n == 0:
+            return (torch.empty(0, dtype=torch.int64, device=dev),
+                    torch.zeros(1, dtype=torch.int64, device=dev),
+                    torch.empty(0, dtype=torch.uint8, device=dev))
+        ptr = np.array([blk.data_ptr() for blk in blocks], dtype=np.int64)
+        first = np.cumsum(nb) - nb
+        # the index sections, back to back: S rows of 16 * n_b bytes
+        index = torch.empty(2 * n, dtype=torch.int64, device=dev)
+        varlen_copy(i64(np.concatenate([[0], np.cumsum(nb)])
+                        * INDEX_ENTRY_BYTES),
+                    i64(ptr + HEADER_BYTES), i64([0, S]),
+                    i64([index.data_ptr()]), total=INDEX_ENTRY_BYTES * n)
+        keys, ends = index[0::2], index[1::2]
+        # `end` restarts in every block: a row starts where the row before
+        # it ends, a block's first row at 0
+        prev = torch.zeros(n, dtype=torch.int64, device=dev)
+        prev[1:] = ends[:-1]
+        prev[i64(first)] = 0
+        lens = ends - prev
+        blk_of = torch.repeat_interleave(
+            torch.arange(S, dtype=torch.int64, device=dev), i64(nb),
+            output_size=n)
+        src = i64(ptr + HEADER_BYTES + INDEX_ENTRY_BYTES * nb)[blk_of] + prev
+        if ordering:
+            from .ops.radix import sort_pairs_aos
+            pr = torch.empty(2 * n, dtype=torch.int64, device=dev)
+            pr[0::2] = keys
+            pr[1::2] = torch.arange(n, dtype=torch.int64, device=dev)
+            pr = sort_pairs_aos(pr, 0, end_bit)
+            keys, order = pr[0::2], pr[1::2]
+            lens, src = lens[order], src[order]
+        offsets = exclusive_scan(lens)
+        data = torch.empty(heap, dtype=torch.uint8, device=dev)
+        varlen_copy(offsets, src.contiguous(), i64([0, n]),
+                    i64([data.data_ptr()]), total=heap)
+        return keys.contiguous(), offsets, data
 
     @property
     def metrics(self) -> TaskMetrics:

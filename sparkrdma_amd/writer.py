@@ -22,6 +22,11 @@ Record model (fixed-width path): a partition segment is AoS —
 scatter's per-digit write bursts and lets the reduce side consume fetched
 chunks without splitting); n is inferable from the segment length. The
 bytes path (arbitrary pickled records) concatenates pickle frames.
+Variable-length rows (u64 key + payload of any length; ``write_varlen``,
+``write_device_varlen``) have the segment format of ``varlen.py``: a
+header, a (key, end) index and a payload heap per partition, placed by the
+same ``_GpuLayout`` and written by one byte-balanced copy
+(ops/csrc/varlen.hip).
 """
 
 from __future__ import annotations
@@ -183,6 +188,8 @@ class ShuffleWriter:
         self._gpu_batches: list = []      # (keys, values) device tensors
         self._gpu_records: list = []      # flat uint8 device tensors
         self._record_shape: Optional[tuple] = None  # (record, key) bytes
+        self._varlen_batches: list = []   # (keys, offsets, data) numpy
+        self._gpu_varlen: list = []       # (keys, offsets, data) device
         self._stopped = False
 
     # -- fixed-width tensor path ---------------------------------------
@@ -190,6 +197,7 @@ class ShuffleWriter:
     def write_batch(self, keys: np.ndarray, values: Optional[np.ndarray] = None) -> None:
         if values is not None and len(values) != len(keys):
             raise ValueError("keys/values length mismatch")
+        self._check_lane("write_batch")
         self._key_batches.append(np.ascontiguousarray(keys, dtype=np.uint64))
         self._value_batches.append(
             None if values is None else np.ascontiguousarray(values, dtype=np.uint8))
@@ -199,6 +207,7 @@ class ShuffleWriter:
     def write_device_batch(self, keys, values=None) -> None:
         """keys/values: int64 CUDA tensors. Partitioned and serialized by
         the radix kernel straight into HBM pool blocks at stop()."""
+        self._check_lane("write_device_batch")
         self._gpu_batches.append((keys, values))
 
     def write_device_records(self, records, record_bytes: int,
@@ -219,6 +228,7 @@ class ShuffleWriter:
         prev = self._record_shape
         if prev is not None and prev != (record_bytes, key_bytes):
             raise ValueError("record shape changed between batches")
+        self._check_lane("write_device_records")
         self._record_shape = (record_bytes, key_bytes)
         self._gpu_records.append(records)
 
@@ -230,6 +240,7 @@ class ShuffleWriter:
         ``partition_ids`` for integer keys); default is pickled-key crc32
         (stable across processes)."""
         R = self.handle.num_partitions
+        self._check_lane("write_records")
         if self._byte_records is None:
             self._byte_records = [[] for _ in range(R)]
         import zlib
@@ -252,6 +263,71 @@ class ShuffleWriter:
                                  f"outside [0, {R})")
             self._byte_records[pid].append(pickle.dumps((k, v), protocol=4))
             self.metrics.records_written += 1
+
+    # -- variable-length rows (varlen.py has the wire format) -----------
+
+    def _check_lane(self, lane: str) -> None:
+        """The variable-length lanes have a segment format of their own:
+        a writer takes either them or the other write_* lanes, and only
+        one of the two variable-length lanes."""
+        varlen = lane in ("write_varlen", "write_device_varlen")
+        used = {
+            "write_batch": bool(self._key_batches),
+            "write_device_batch": bool(self._gpu_batches),
+            "write_device_records": bool(self._gpu_records),
+            "write_records": self._byte_records is not None,
+            "write_varlen": bool(self._varlen_batches),
+            "write_device_varlen": bool(self._gpu_varlen),
+        }
+        for other, on in used.items():
+            if on and other != lane and (
+                    varlen or other in ("write_varlen",
+                                        "write_device_varlen")):
+                raise ValueError(f"{lane} cannot be mixed with {other} in "
+                                 "one writer")
+
+    def write_varlen(self, keys, offsets, data) -> None:
+        """CPU lane for rows of a u64 key and a payload of any length, in
+        the CSR / Arrow binary layout: ``keys`` numpy u64[n], ``offsets``
+        int64[n + 1] with ``offsets[0] == 0``, row r is
+        ``data[offsets[r]:offsets[r + 1]]`` of the uint8 array ``data``.
+        Several batches concatenate. Offsets that are not such a scan
+        raise ValueError here. Read back with ``read_varlen``."""
+        from .varlen import check_offsets
+        self._check_lane("write_varlen")
+        keys = np.ascontiguousarray(keys).astype(np.uint64, copy=False) \
+            .reshape(-1)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        check_offsets(offsets, len(keys), len(data))
+        self._varlen_batches.append((keys, offsets, data))
+
+    def write_device_varlen(self, keys, offsets, data) -> None:
+        """GPU lane of ``write_varlen``: ``keys`` int64[n] (u64 bits),
+        ``offsets`` int64[n + 1] and ``data`` uint8 are CUDA tensors.
+        Nothing is read here and the call does not synchronise; the rows
+        are partitioned and laid out in HBM pool blocks at stop()
+        (ops/csrc/varlen.hip), and the offsets are checked there:
+        ``offsets[0] == 0``, non-decreasing, ``offsets[-1] <=
+        data.numel()`` — a violation raises ValueError from stop() before
+        anything is published.
+
+        Limits: a partitioner with ``gpu_params()`` that is not a search of
+        split points, at most 4096 partitions, no map-side combine."""
+        import torch
+        self._check_lane("write_device_varlen")
+        for t, name, dt in ((keys, "keys", torch.int64),
+                            (offsets, "offsets", torch.int64),
+                            (data, "data", torch.uint8)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt \
+                    or t.dim() != 1 or not t.is_cuda:
+                raise ValueError(f"{name} must be a 1-D {dt} CUDA tensor")
+        if offsets.numel() != keys.numel() + 1:
+            raise ValueError(f"offsets has {offsets.numel()} entries for "
+                             f"{keys.numel()} keys, expected "
+                             f"{keys.numel() + 1}")
+        self._gpu_varlen.append((keys.contiguous(), offsets.contiguous(),
+                                 data.contiguous()))
 
     # -- commit ---------------------------------------------------------
 
@@ -283,11 +359,17 @@ class ShuffleWriter:
             return
         if combiner is not None:
             self._check_combiner(combiner, combine_key_bits)
+        if success and self._gpu_varlen:
+            self._check_gpu_varlen(partitioner)
         self._stopped = True
         if not success:
             return
         t0 = time.perf_counter_ns()
-        if self._gpu_records:
+        if self._gpu_varlen:
+            self._commit_gpu_varlen(partitioner)
+        elif self._varlen_batches:
+            self._commit_varlen(partitioner)
+        elif self._gpu_records:
             self._commit_gpu_records(partitioner)
         elif self._gpu_batches:
             self._commit_gpu(partitioner, combiner, combine_key_bits)
@@ -316,6 +398,10 @@ class ShuffleWriter:
         if self._byte_records is not None:
             raise ValueError("map-side combine does not cover the pickled "
                              "lane (write_records)")
+        if self._varlen_batches or self._gpu_varlen:
+            raise ValueError("map-side combine does not cover "
+                             "variable-length rows (write_varlen, "
+                             "write_device_varlen)")
         for _k, v in self._gpu_batches:
             if v is None:
                 raise ValueError("map-side combine needs values; a "
@@ -570,6 +656,142 @@ class ShuffleWriter:
             layout = _GpuLayout(self, counts[:R] * W, 1 << nbits_eff, dev)
             group_records(recs, W, pairs, n, shift, nbits_eff, hist, counts,
                           layout.dst, func, nparts)
+        layout.finish(n)
+
+    # -- variable-length rows -------------------------------------------
+
+    VARLEN_MAX_PARTITIONS = 4096
+
+    def _commit_varlen(self, partitioner) -> None:
+        """CPU lane: the numpy mirror of _commit_gpu_varlen."""
+        from .varlen import concat_rows, partition_varlen_np
+        keys, offsets, data = concat_rows(self._varlen_batches)
+        pids = partitioner.partition_ids(keys)
+        self.metrics.records_written += len(keys)
+        self._commit_segments(partition_varlen_np(
+            keys, offsets, data, pids, self.handle.num_partitions))
+
+    def _check_gpu_varlen(self, partitioner) -> None:
+        """Reject what the GPU variable-length lane does not cover, before
+        any state changes."""
+        R = self.handle.num_partitions
+        limit = self.VARLEN_MAX_PARTITIONS
+        if R > limit:
+            raise ValueError(
+                f"write_device_varlen supports R <= {limit} partitions, got "
+                f"{R}; use write_varlen (the CPU lane) beyond that")
+        func = self._gpu_part_params(partitioner)[0]
+        if func == PART_BOUNDS:
+            raise ValueError(
+                "write_device_varlen does not cover split-point partitioners "
+                "(a search of gpu_bounds()); it takes partitioners whose "
+                f"gpu_params() is a closed form, at R <= {limit}")
+
+    def _commit_gpu_varlen(self, partitioner) -> None:
+        """Map-side GPU write of variable-length rows. (key, row id) pairs
+        run the 16-byte pair machinery and are grouped by partition; the
+        lengths follow in grouped order and their scan places every
+        payload; ONE byte-balanced copy (ops/csrc/varlen.hip) then writes
+        every partition's segment — header, index, heap, padding — to its
+        final position in the HBM pool blocks. The header plus index slab of
+        a partition is built with torch on the device and copied as one
+        long row; the padding is a row of zeros."""
+        import torch
+        from .ops.radix import digit_counts, scatter_pairs
+        from .ops.varlen import exclusive_scan, varlen_copy
+        from .varlen import ALIGN, HEADER_BYTES, INDEX_ENTRY_BYTES
+        if self.manager.gpu is None:
+            raise RuntimeError("GPU writer requires the GPU data plane")
+        R = self.handle.num_partitions
+        func, shift, nparts, nbits_eff = self._gpu_part_params(partitioner)
+        nd = 1 << nbits_eff
+        batches = self._gpu_varlen
+        n = sum(b[0].numel() for b in batches)
+        if n == 0:
+            self._commit_empty()
+            return
+        dev = batches[0][0].device
+        # rows of all batches: length and source address; the offsets check
+        # stays on the device until the counts come back
+        bad = torch.zeros((), dtype=torch.bool, device=dev)
+        lens, addrs = [], []
+        for _k, off, data in batches:
+            d = off[1:] - off[:-1]
+            bad = bad | (off[0] != 0) | (off[-1] > data.numel())
+            if d.numel():
+                bad = bad | (d.min() < 0)
+            lens.append(d)
+            addrs.append(off[:-1] + data.data_ptr())
+        lens = lens[0] if len(lens) == 1 else torch.cat(lens)
+        addrs = addrs[0] if len(addrs) == 1 else torch.cat(addrs)
+        pr = torch.empty(2 * n, dtype=torch.int64, device=dev)
+        pr[0::2] = batches[0][0] if len(batches) == 1 \
+            else torch.cat([b[0] for b in batches])
+        pr[1::2] = torch.arange(n, dtype=torch.int64, device=dev)
+        # group the pairs by partition id; the bases come from the device
+        # scan of the digit totals, so nothing waits for the host yet
+        hist, totals = digit_counts(pr.data_ptr(), n, shift, nbits_eff, dev,
+                                    func, 2, nparts)
+        cnt = totals.to(torch.int64)
+        ends = torch.cumsum(cnt, 0)
+        starts = ends - cnt
+        grouped = torch.empty_like(pr)
+        scatter_pairs(pr, n, shift, nbits_eff, hist,
+                      grouped.data_ptr() + starts * 16, func, nparts)
+        rid = grouped[1::2]
+        glen = lens[rid]
+        gcum = exclusive_scan(glen)
+        heap = gcum[ends] - gcum[starts]
+        # THE host sync: per-partition rows, payload bytes, offsets verdict
+        host = torch.cat([cnt, heap, bad.to(torch.int64).reshape(1)]) \
+            .cpu().numpy()
+        if host[-1]:
+            raise ValueError(
+                "write_device_varlen: offsets must start at 0, be "
+                "non-decreasing and end inside data")
+        counts, heaps = host[:nd], host[nd:2 * nd]
+        if counts[R:].any():
+            raise ValueError("partitioner produced an id >= "
+                             f"{R} on the GPU")
+        slab = np.where(counts > 0,
+                        HEADER_BYTES + INDEX_ENTRY_BYTES * counts, 0)
+        seg_bytes = -(-(slab + heaps) // ALIGN) * ALIGN
+        layout = _GpuLayout(self, seg_bytes[:R], nd, dev)
+        # header + index slabs of all partitions in one int64 tensor:
+        # partition p's at word 2 * (starts[p] + p)
+        ar_nd = torch.arange(nd, dtype=torch.int64, device=dev)
+        ar_n = torch.arange(n, dtype=torch.int64, device=dev)
+        pid = torch.repeat_interleave(ar_nd, cnt, output_size=n)
+        idx = torch.empty(2 * (n + nd), dtype=torch.int64, device=dev)
+        hp = 2 * (starts + ar_nd)
+        idx[hp] = cnt
+        idx[hp + 1] = heap
+        rp = 2 * (ar_n + pid + 1)
+        idx[rp] = grouped[0::2]
+        idx[rp + 1] = gcum[1:] - gcum[starts][pid]
+        # the rows of the copy, in destination order: per partition its
+        # slab, its payloads, its zero padding (empty partitions: rows of
+        # length 0, which own no byte)
+        m = n + 2 * nd
+        zeros = torch.zeros(ALIGN, dtype=torch.uint8, device=dev)
+        slab_t = torch.from_numpy(slab).to(dev)
+        pad_t = torch.from_numpy(seg_bytes - slab - heaps).to(dev)
+        e_slab = starts + 2 * ar_nd
+        e_row = ar_n + 2 * pid + 1
+        e_pad = ends + 2 * ar_nd + 1
+        row_len = torch.empty(m, dtype=torch.int64, device=dev)
+        row_src = torch.empty(m, dtype=torch.int64, device=dev)
+        row_len[e_slab] = slab_t
+        row_src[e_slab] = idx.data_ptr() + 8 * hp
+        row_len[e_row] = glen
+        row_src[e_row] = addrs[rid]
+        row_len[e_pad] = pad_t
+        row_src[e_pad] = zeros.data_ptr()
+        seg_first = torch.cat([e_slab, torch.tensor([m], dtype=torch.int64,
+                                                    device=dev)])
+        varlen_copy(exclusive_scan(row_len), row_src, seg_first,
+                    torch.from_numpy(layout.dst).to(dev),
+                    total=int(seg_bytes.sum()))
         layout.finish(n)
 
     def _commit_empty(self) -> None:
