@@ -1496,12 +1496,14 @@ static void scatter_launch(const uint64_t* keys, const uint64_t* vals,
   size_t lds = (size_t)TILE * 8 + (size_t)NW * ND * 4 + (size_t)ND * 4 * 2 +
                BLOCK * 4;
   auto kfn = radix_scatter_kernel<NBITS, HAS_VAL>;
-  static bool attr_set[13] = {};
-  if (lds > 64 * 1024 && !attr_set[NBITS]) {
+  // one flag per <NBITS, HAS_VAL>: the keys+vals and keys-only kernels
+  // are different functions, each needs the attribute set on itself
+  static bool attr_set = false;
+  if (lds > 64 * 1024 && !attr_set) {
     (void)hipFuncSetAttribute(
         reinterpret_cast<const void*>(kfn),
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set[NBITS] = true;
+    attr_set = true;
   }
   hipLaunchKernelGGL(kfn, dim3(nb), dim3(BLOCK), lds, s, keys, vals, n, shift,
                      hist, nb, key_dst, val_dst, func, aos_out, in_stride,

@@ -21,6 +21,53 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def onesweep_passes(start_bit: int, end_bit: int) -> int:
+    """Number of 8-bit onesweep passes over key bits [start_bit, end_bit):
+    ceil((min(end_bit, 64) - start_bit) / 8), 0 for an empty window. This
+    is the count kernels.hip onesweep_sort lays the workspace out for, so
+    every ``onesweep_workspace_bytes`` call of a sort wrapper takes it from
+    here."""
+    bits = min(end_bit, 64) - start_bit
+    return -(-bits // 8) if bits > 0 else 0
+
+
+def _digit_windows(start_bit: int, end_bit: int):
+    """The native sort calls, as (start_bit, end_bit) windows run in order,
+    that leave the rows ordered by bits [start_bit, end_bit).
+
+    A native call steps 8-bit digits up from its start bit, and every pass
+    bins by a full 8-bit digit. That is the window itself when it is a
+    whole number of digits, and also when it reaches bit 64: the last pass
+    is then clamped to bits [56, 64), which only re-covers bits the pass
+    before it ordered. Any other last digit would take in bits ABOVE the
+    window and order the rows by those first, so the last pass runs as a
+    call of its own over the top 8 bits of the window, re-covering bits
+    below it instead. Together the calls make onesweep_passes() passes.
+
+    A window that ends below bit 8 has no 8 bits at or below its top: its
+    one pass bins by bits [start_bit, start_bit + 8), which orders the
+    rows by the window only when the bits from end_bit up to there are
+    equal in all keys (the "shared top bits" case of the readers)."""
+    end_bit = min(end_bit, 64)
+    bits = end_bit - start_bit
+    if bits <= 0:
+        return []
+    if bits % 8 == 0 or end_bit == 64 or end_bit < 8:
+        return [(start_bit, end_bit)]
+    whole = start_bit + bits // 8 * 8
+    head = [(start_bit, whole)] if whole > start_bit else []
+    return head + [(end_bit - 8, end_bit)]
+
+
+def _check_small_digit(nbits: int, shift: int, func: int) -> None:
+    """The kernels bin by at least 4 bits. A narrower digit runs the 4-bit
+    kernel, which is the same partition only where the extra mask bits
+    read zeros: the digit is the TOP nbits of the (mixed) key."""
+    if nbits < 4 and func in (0, 1) and shift != 64 - nbits:
+        raise ValueError(f"nbits={nbits} < 4 needs shift == 64 - nbits "
+                         f"(the top bits of the key), got shift={shift}")
+
+
 def digit_counts(src: int, n: int, shift: int, nbits_eff: int, device,
                  func: int = 0, in_stride: int = 1, nparts: int = 0,
                  totals: Optional[torch.Tensor] = None
@@ -76,18 +123,24 @@ def radix_partition(keys: torch.Tensor, vals: Optional[torch.Tensor],
     meaningfully. Otherwise contiguous outputs are allocated and per-digit
     bases derived from the counts.
 
+    nbits < 4 is served only as the top nbits of the key (the default
+    shift); any other shift raises ValueError.
+
     Returns (counts u32[2^nbits] on device, keys_out, vals_out).
     """
-    m = load()
     n = keys.numel()
     assert keys.dtype in (torch.int64, torch.uint64), "keys must be 64-bit"
     if shift is None:
         shift = 64 - nbits
-    nbits_eff = max(nbits, 4)  # kernel instantiations start at 4 bits; the
-    nd = 1 << nbits_eff        # extra mask bits read zeros above the digit
+    # kernel instantiations start at 4 bits; with shift == 64 - nbits the
+    # extra mask bits read the zeros the shift brings in above the digit
+    nbits_eff = max(nbits, 4)
+    nd = 1 << nbits_eff
     dev = keys.device
     if hash_mix and nbits_eff != nbits:
         raise ValueError("hash partitioning requires nbits >= 4")
+    _check_small_digit(nbits, shift, int(hash_mix))
+    m = load()
     hist, totals = digit_counts(keys.data_ptr(), n, shift, nbits_eff, dev,
                                 int(hash_mix))
     keys_out = vals_out = None
@@ -116,11 +169,14 @@ def partition_aos(keys: torch.Tensor, vals: torch.Tensor, nbits: int,
     buckets laid out contiguously — the stage-mode (RCCL alltoallv) send
     buffer in a single scatter pass.
 
+    nbits < 4 needs the default shift, as in radix_partition.
+
     Returns (counts int32[2^nbits] device, pairs int64[2n] device)."""
-    m = load()
     n = keys.numel()
     if shift is None:
         shift = 64 - nbits
+    _check_small_digit(nbits, shift, int(hash_mix))
+    m = load()
     nbits_eff = max(nbits, 4)
     dev = keys.device
     hist, totals = digit_counts(keys.data_ptr(), n, shift, nbits_eff, dev,
@@ -145,27 +201,37 @@ def sort_pairs_aos(pairs: torch.Tensor, start_bit: int = 0,
     One dwordx4 load + one dwordx4 store per record per pass, and digit
     write bursts twice as long as the SoA path (measured 2x scattered
     write bandwidth at 256 B vs 128 B — profiles/r01_kernel_profile.md).
+
+    Guarantee: the output is ordered by key bits [start_bit, end_bit)
+    (end_bit is capped at 64). It is STABLE with respect to that window
+    only when the window is a whole number of 8-bit digits that does not
+    run past bit 64; otherwise the last pass re-covers bits next to its
+    digit (_digit_windows), so rows equal in the window may come out
+    ordered by those bits. The result is ``pairs`` itself after an even
+    number of passes (onesweep_passes) and ``tmp`` after an odd one.
+    ``ws`` needs onesweep_workspace_bytes(n, onesweep_passes(...)) bytes.
     """
     m = load()
     n = pairs.numel() // 2
     if n == 0:
         return pairs
-    bits = min(end_bit, 64) - start_bit
-    passes = -(-bits // 8)
     if tmp is None:
         tmp = torch.empty_like(pairs)
     else:
         assert tmp.numel() >= pairs.numel(), "tmp too small"
         tmp = tmp[:pairs.numel()]
-    need_ws = m.onesweep_workspace_bytes(n, passes)
+    need_ws = m.onesweep_workspace_bytes(n, onesweep_passes(start_bit,
+                                                            end_bit))
     if ws is None:
         ws = torch.empty(need_ws, dtype=torch.uint8, device=pairs.device)
     else:
         assert ws.numel() >= need_ws, "ws too small"
-    res = m.onesweep_sort_aos_u64(pairs.data_ptr(), tmp.data_ptr(), n,
-                                  start_bit, start_bit + bits, ws.data_ptr(),
-                                  _stream())
-    return pairs if res == 0 else tmp
+    cur, other = pairs, tmp
+    for lo, hi in _digit_windows(start_bit, end_bit):
+        if m.onesweep_sort_aos_u64(cur.data_ptr(), other.data_ptr(), n,
+                                   lo, hi, ws.data_ptr(), _stream()):
+            cur, other = other, cur
+    return cur
 
 
 def reduce_by_key_aos(pairs: torch.Tensor, op: str,
@@ -441,10 +507,13 @@ def partition_records(recs: torch.Tensor, rec_bytes: int,
                       nparts: int = 0):
     """Group W-byte records into 2^nbits contiguous buckets (digit from
     the key prefix) — the stage-mode (RCCL alltoall) send-buffer builder
-    for wide records. Returns (counts int64 numpy, grouped records)."""
+    for wide records. nbits < 4 with a bit-extraction func (0, 1) needs
+    the default shift, as in radix_partition.
+    Returns (counts int64 numpy, grouped records)."""
     n = recs.numel() // rec_bytes
     if shift is None:
         shift = 64 - nbits
+    _check_small_digit(nbits, shift, func)
     nbits_eff = max(nbits, 4)
     pairs = extract_pairs(recs, rec_bytes, key_bytes)
     hist, totals = digit_counts(pairs.data_ptr(), n, shift, nbits_eff,
@@ -467,6 +536,15 @@ def sort_pairs(keys: torch.Tensor, vals: Optional[torch.Tensor] = None,
     the top bits pass end_bit = 64 - log2(R) and save whole passes.
     Uses the decoupled-lookback onesweep path (one kernel per pass) when
     n < 2^30; the 3-kernel hist/scan/scatter path otherwise.
+
+    Guarantee: the output is ordered by key bits [start_bit, end_bit)
+    (end_bit is capped at 64). It is STABLE with respect to that window
+    only when the window is a whole number of 8-bit digits that does not
+    run past bit 64; otherwise the last pass re-covers bits next to its
+    digit (_digit_windows), so rows equal in the window may come out
+    ordered by those bits. The result is in the input tensors after an
+    even number of passes (onesweep_passes) and in fresh ones after an
+    odd one.
     """
     m = load()
     n = keys.numel()
@@ -475,28 +553,25 @@ def sort_pairs(keys: torch.Tensor, vals: Optional[torch.Tensor] = None,
     dev = keys.device
     tmp_k = torch.empty_like(keys)
     tmp_v = torch.empty_like(vals) if vals is not None else None
-    end_bit = start_bit + ((end_bit - start_bit + 7) // 8) * 8  # whole digits
-    end_bit = min(end_bit, 64)
-    passes = (end_bit - start_bit) // 8
     if onesweep is None:
         onesweep = n < (1 << 30)
     if onesweep:
-        ws = torch.empty(m.onesweep_workspace_bytes(n, passes),
-                         dtype=torch.uint8, device=dev)
-        res = m.onesweep_sort_pairs_u64(
-            keys.data_ptr(), vals.data_ptr() if vals is not None else 0,
-            tmp_k.data_ptr(), tmp_v.data_ptr() if tmp_v is not None else 0,
-            n, start_bit, end_bit, ws.data_ptr(), _stream())
+        sort = m.onesweep_sort_pairs_u64
+        ws_bytes = m.onesweep_workspace_bytes(
+            n, onesweep_passes(start_bit, end_bit))
     else:
-        ws = torch.empty(m.sort_workspace_bytes(n), dtype=torch.uint8,
-                         device=dev)
-        res = m.sort_pairs_u64(
-            keys.data_ptr(), vals.data_ptr() if vals is not None else 0,
-            tmp_k.data_ptr(), tmp_v.data_ptr() if tmp_v is not None else 0,
-            n, start_bit, end_bit, ws.data_ptr(), _stream())
-    if res == 0:
-        return keys, vals
-    return tmp_k, tmp_v
+        sort = m.sort_pairs_u64
+        ws_bytes = m.sort_workspace_bytes(n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    cur, other = (keys, vals), (tmp_k, tmp_v)
+    for lo, hi in _digit_windows(start_bit, end_bit):
+        if sort(cur[0].data_ptr(),
+                cur[1].data_ptr() if vals is not None else 0,
+                other[0].data_ptr(),
+                other[1].data_ptr() if vals is not None else 0,
+                n, lo, hi, ws.data_ptr(), _stream()):
+            cur, other = other, cur
+    return cur
 
 
 class AosSorter:
@@ -511,16 +586,16 @@ class AosSorter:
         m = load()
         self.n = n
         self.start_bit = start_bit
-        self.end_bit = min(start_bit + ((end_bit - start_bit + 7) // 8) * 8, 64)
-        passes = (self.end_bit - start_bit) // 8
+        self.end_bit = min(end_bit, 64)
         self.tmp = torch.empty(2 * n, dtype=torch.int64, device=device)
-        self.ws = torch.empty(m.onesweep_workspace_bytes(n, passes),
-                              dtype=torch.uint8, device=device)
+        self.ws = torch.empty(
+            m.onesweep_workspace_bytes(n, onesweep_passes(start_bit, end_bit)),
+            dtype=torch.uint8, device=device)
         self._m = m
 
     def sort_(self, pairs: torch.Tensor) -> torch.Tensor:
+        """sort_pairs_aos(pairs, start_bit, end_bit) on the held buffers:
+        same ordering guarantee, same rule for which buffer comes back."""
         assert pairs.numel() == 2 * self.n
-        res = self._m.onesweep_sort_aos_u64(
-            pairs.data_ptr(), self.tmp.data_ptr(), self.n, self.start_bit,
-            self.end_bit, self.ws.data_ptr(), _stream())
-        return pairs if res == 0 else self.tmp
+        return sort_pairs_aos(pairs, self.start_bit, self.end_bit,
+                              tmp=self.tmp, ws=self.ws)
