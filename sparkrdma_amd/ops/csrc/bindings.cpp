@@ -92,18 +92,6 @@ PYBIND11_MODULE(_hipshuffle, m) {
         py::arg("dstart") = 0, py::arg("shift") = 0, py::arg("mask") = 0,
         py::arg("func") = 0, py::arg("nparts") = 0, py::arg("stream") = 0,
         py::arg("segs") = 0, py::arg("nsegs") = 0);
-  m.def("onesweep_sort_aos_word_u64", &hs::onesweep_sort_aos_word_u64,
-        py::arg("pairs"), py::arg("tmp_pairs"), py::arg("n"),
-        py::arg("start_bit"), py::arg("end_bit"), py::arg("ws"),
-        py::arg("stream") = 0, py::arg("sort_word") = 0,
-        py::call_guard<py::gil_scoped_release>());
-  m.def("onesweep_sort_aos_fused_u64", &hs::onesweep_sort_aos_fused_u64,
-        py::arg("pairs"), py::arg("tmp_pairs"), py::arg("n"),
-        py::arg("start_bit"), py::arg("end_bit"), py::arg("ws"),
-        py::arg("stream") = 0, py::arg("sort_word") = 0,
-        py::arg("recs") = 0, py::arg("out") = 0, py::arg("rec_bytes") = 0,
-        py::arg("segs") = 0, py::arg("nsegs") = 0,
-        py::call_guard<py::gil_scoped_release>());
   m.def("sort_workspace_bytes", &hs::sort_workspace_bytes);
   m.def("sort_pairs_u64", &hs::sort_pairs_u64, py::arg("keys"),
         py::arg("vals"), py::arg("tmp_keys"), py::arg("tmp_vals"),
@@ -131,7 +119,9 @@ PYBIND11_MODULE(_hipshuffle, m) {
           return py::make_tuple(lo_bit, passes, run_bits);
         },
         py::arg("n"), py::arg("end_bit") = 64);
-  m.def("sort_records_truncated_u64", &hs::sort_records_truncated_u64,
+  m.def("sort_records_workspace_bytes", &hs::sort_records_workspace_bytes,
+        py::arg("n"), py::arg("end_bit") = 64, py::arg("key_bytes") = 10);
+  m.def("sort_records_u64", &hs::sort_records_u64,
         py::arg("pairs"), py::arg("tmp_pairs"), py::arg("n"),
         py::arg("end_bit"), py::arg("key_bytes"), py::arg("ws"),
         py::arg("stream"), py::arg("recs"), py::arg("out"),
@@ -140,7 +130,8 @@ PYBIND11_MODULE(_hipshuffle, m) {
   m.def("onesweep_sort_aos_u64", &hs::onesweep_sort_aos_u64,
         py::arg("pairs"), py::arg("tmp_pairs"), py::arg("n"),
         py::arg("start_bit"), py::arg("end_bit"), py::arg("ws"),
-        py::arg("stream") = 0, py::call_guard<py::gil_scoped_release>());
+        py::arg("stream") = 0, py::arg("sort_word") = 0,
+        py::call_guard<py::gil_scoped_release>());
   m.def("onesweep_sort_pairs_u64", &hs::onesweep_sort_pairs_u64,
         py::arg("keys"), py::arg("vals"), py::arg("tmp_keys"),
         py::arg("tmp_vals"), py::arg("n"), py::arg("start_bit"),

@@ -62,7 +62,7 @@ void extract_pairs(uintptr_t recs, uint64_t n, uint32_t rec_bytes,
                    int pid_func = -1, int pid_shift = 0,
                    uint32_t pid_mask = 0, uint32_t pid_nparts = 0,
                    uint64_t idx_base = 0);
-// segs / nsegs (here and in the fused sorts below): a device table of
+// segs / nsegs (here and in sort_records_u64 below): a device table of
 // {u64 first_rec, const u32* base} entries sorted by first_rec and covering
 // every record index; record idx is read at
 // base[s] + (idx - first_rec[s]) * rec_bytes for the last s with
@@ -99,32 +99,28 @@ void join_emit(uintptr_t a_keys, uintptr_t a_vals, uint32_t na,
                uintptr_t out_b, uintptr_t stream);
 size_t onesweep_workspace_bytes(uint32_t n, int passes);
 void set_timing_buf(uintptr_t p);
+// sort_word: the u64 of each 16-byte pair whose bits order the pairs
 int onesweep_sort_aos_u64(uintptr_t pairs, uintptr_t tmp_pairs, uint32_t n,
                           int start_bit, int end_bit, uintptr_t ws,
-                          uintptr_t stream);
-int onesweep_sort_aos_word_u64(uintptr_t pairs, uintptr_t tmp_pairs,
-                               uint32_t n, int start_bit, int end_bit,
-                               uintptr_t ws, uintptr_t stream,
-                               int sort_word);
-int onesweep_sort_aos_fused_u64(uintptr_t pairs, uintptr_t tmp_pairs,
-                                uint32_t n, int start_bit, int end_bit,
-                                uintptr_t ws, uintptr_t stream,
-                                int sort_word, uintptr_t recs,
-                                uintptr_t out, uint32_t rec_bytes,
-                                uintptr_t segs = 0, uint32_t nsegs = 0);
-// truncated wide-record sort with tie repair (kernels.hip)
+                          uintptr_t stream, int sort_word = 0);
+// Wide-record sort (kernels.hip): the extracted pairs in, the sorted records
+// in `out`, always. Returns the path taken, as last_sort_path() reports it:
+// 0 full pass sequence, 1 truncated sort with tie repair, 2 truncated, then
+// full because a tied run was too long. Blocks on the stream once when a
+// truncated attempt ran (paths 1 and 2), else never.
+int sort_records_u64(uintptr_t pairs, uintptr_t tmp_pairs, uint32_t n,
+                     int end_bit, int key_bytes, uintptr_t ws,
+                     uintptr_t stream, uintptr_t recs, uintptr_t out,
+                     uint32_t rec_bytes, int fuse = 1, uintptr_t segs = 0,
+                     uint32_t nsegs = 0);
+// bytes of its ws, whichever path it takes
+size_t sort_records_workspace_bytes(uint32_t n, int end_bit, int key_bytes);
 void set_tie_repair(int m);
 int last_sort_path();
 int tie_repair_tile();
 int tie_repair_max_run();
 void sort_records_plan(uint32_t n, int end_bit, int* lo_bit, int* passes,
                        int* run_bits);
-int sort_records_truncated_u64(uintptr_t pairs, uintptr_t tmp_pairs,
-                               uint32_t n, int end_bit, int key_bytes,
-                               uintptr_t ws, uintptr_t stream,
-                               uintptr_t recs, uintptr_t out,
-                               uint32_t rec_bytes, int fuse,
-                               uintptr_t segs = 0, uint32_t nsegs = 0);
 int onesweep_sort_pairs_u64(uintptr_t keys, uintptr_t vals,
                             uintptr_t tmp_keys, uintptr_t tmp_vals,
                             uint32_t n, int start_bit, int end_bit,

@@ -1240,8 +1240,8 @@ void extract_records(uintptr_t src, uint64_t n, uint32_t rec_bytes,
 }
 
 // ---------------------------------------------------------------------------
-// Tie repair for the truncated wide-record sort (sort_records_truncated_u64
-// below). The pairs arrive stably ordered by the RUN BITS only — prefix
+// Tie repair for the truncated wide-record sort (sort_records_u64 below).
+// The pairs arrive stably ordered by the RUN BITS only — prefix
 // bits [lo_bit, top), selected by run_mask — so elements that agree on
 // them are adjacent and in input order. With 2^run_bits >= 8n such runs
 // are rare and short for non-degenerate keys, and ordering each of them
@@ -1604,7 +1604,9 @@ size_t sort_workspace_bytes(uint32_t n) {
 }
 
 // Onesweep sort: ws layout = totals u32[passes*256] | key_dst u64[256] |
-// val_dst u64[256] | ticket u32 (+pad) | desc u32[nb*256].
+// val_dst u64[256] | ticket u32, tie flag u32 (+pad to 16) |
+// desc u32[nb*256]. The ticket slot is zeroed before every pass; the tie
+// flag is the overflow word of tie_repair_kernel (truncated sort only).
 constexpr int OS_ITEMS = 16;  // SoA: 4096-elem tiles @ 256 threads
 constexpr int OS_AOS_BS = 512;  // AoS: 4096-elem tiles @ 512 threads,
 constexpr int OS_AOS_ITEMS = 8;  // 2 blocks/CU resident
@@ -1628,27 +1630,47 @@ size_t onesweep_workspace_bytes(uint32_t n, int passes) {
          (size_t)nb * 256 * 8;
 }
 
-// aos = 0: keys/vals are separate u64 arrays (SoA).
-// aos = 1: keys/tmp_keys point at interleaved (key,val) 16-byte records;
-//          vals/tmp_vals ignored.
-static int onesweep_sort(uintptr_t keys, uintptr_t vals,
-                         uintptr_t tmp_keys, uintptr_t tmp_vals,
-                         uint32_t n, int start_bit, int end_bit,
-                         uintptr_t ws, hipStream_t s, int aos,
-                         int sort_word = 0, uintptr_t fuse_recs = 0,
-                         uintptr_t fuse_out = 0,
-                         uint32_t fuse_rec_bytes = 0,
-                         uint64_t tie_run_mask = 0,
-                         uint64_t tie_lo_mask = 0,
-                         uint32_t* tie_flag = nullptr,
-                         uintptr_t fuse_segs = 0,
-                         uint32_t fuse_nsegs = 0) {
+// The two buffers a sort ping-pongs between. AoS: keys / tmp_keys point at
+// interleaved (key, val) 16-byte pairs and vals / tmp_vals are unused.
+// SoA: keys and vals are separate u64 arrays (vals may be 0: keys only).
+enum class PairLayout { AoS, SoA };
+struct PairBufs {
+  uintptr_t keys, tmp_keys;
+  uintptr_t vals = 0, tmp_vals = 0;
+  PairLayout layout = PairLayout::AoS;
+};
+// which u64 of an AoS pair a sort orders by: the key prefix, or the aux
+// word, whose bits [48, 64) hold the low 16 bits of an 80-bit key
+constexpr int kPrefixWord = 0, kAuxWord = 1;
+// Where the records of an AoS sort are and where its final pass writes
+// them whole, in sorted order. segs / nsegs: record_src (hipshuffle.h).
+struct RecordTarget {
+  uintptr_t recs, out, segs;
+  uint32_t rec_bytes, nsegs;
+};
+// Tie repair before the final pass of a truncated sort (tie_repair_kernel).
+// flag is set by onesweep_sort: the device word of its ws layout, zero
+// before the kernel runs, that the kernel raises on a run too long.
+struct TieRepair {
+  uint64_t run_mask, lo_mask;
+  uint32_t* flag = nullptr;
+};
+
+// Returns which buffer holds the result: 0 = keys/vals, 1 = the tmp ones;
+// -1 when `fuse` was asked for and no pass ran to carry it (an empty bit
+// window): nothing is written to fuse->out then. tie needs fuse.
+static int onesweep_sort(PairBufs b, uint32_t n, int start_bit, int end_bit,
+                         uintptr_t ws, hipStream_t s,
+                         int sort_word = kPrefixWord,
+                         const RecordTarget* fuse = nullptr,
+                         TieRepair* tie = nullptr) {
   constexpr int PBITS = 8;
   constexpr int PD = 1 << PBITS;
-  // fusion is asked for by naming a record source: fuse_recs, or a
-  // segment table (record_src), with which fuse_recs is unused and may be 0
-  const bool want_fuse = fuse_recs || fuse_nsegs;
-  if (fuse_nsegs && !fuse_segs)
+  const bool aos = b.layout == PairLayout::AoS;
+  // fusion is asked for by naming a record source: recs, or a segment
+  // table (record_src), with which recs is unused and may be 0
+  const bool want_fuse = fuse && (fuse->recs || fuse->nsegs);
+  if (fuse && fuse->nsegs && !fuse->segs)
     throw std::runtime_error("fused sort: nsegs without a table");
   uint32_t nb = os_num_tiles(n);
   int passes = (end_bit - start_bit + PBITS - 1) / PBITS;
@@ -1657,11 +1679,12 @@ static int onesweep_sort(uintptr_t keys, uintptr_t vals,
   uint64_t* val_dst = key_dst + PD;
   uint32_t* ticket = reinterpret_cast<uint32_t*>(val_dst + PD);
   uint64_t* desc = reinterpret_cast<uint64_t*>(ticket + 4);
+  if (tie) tie->flag = ticket + 1;
   HIP_CHECK(hipMemsetAsync(totals, 0, (size_t)passes * PD * 4, s));
   uint32_t hist_grid = nb < 1024 ? (nb ? nb : 1) : 1024;
   hipLaunchKernelGGL((onesweep_hist_all_kernel<10, PBITS>), dim3(hist_grid),
                      dim3(BLOCK), 0, s,
-                     reinterpret_cast<const uint64_t*>(keys), n, start_bit,
+                     reinterpret_cast<const uint64_t*>(b.keys), n, start_bit,
                      passes, totals, aos ? 2 : 1, sort_word);
   HIP_CHECK(hipGetLastError());
   size_t lds_soa = (size_t)OS_TILE * 8 + (size_t)NW * PD * 4 +
@@ -1686,30 +1709,31 @@ static int onesweep_sort(uintptr_t keys, uintptr_t vals,
                                 160 * 1024 - 1024);
     attr_set = true;
   }
-  uintptr_t src_k = keys, src_v = vals, dst_k = tmp_keys, dst_v = tmp_vals;
+  uintptr_t src_k = b.keys, src_v = b.vals, dst_k = b.tmp_keys,
+            dst_v = b.tmp_vals;
   int cur = 0;
   for (int p = 0; p < passes; ++p) {
     int sb = start_bit + p * PBITS;
     if (sb > 64 - PBITS) sb = 64 - PBITS;  // same clamp as hist_all
-    // fused final pass: the writeout copies whole records to fuse_out
+    // fused final pass: the writeout copies whole records to fuse->out
     // (the gather folded into the sort — key_dst becomes record bases)
-    const bool fuse = want_fuse && aos && p == passes - 1;
+    const bool fused = want_fuse && aos && p == passes - 1;
     hipLaunchKernelGGL((onesweep_digit_bases_kernel<PD>), dim3(1),
                        dim3(BLOCK), 0, s, totals, p,
-                       fuse ? (uint64_t)fuse_out : (uint64_t)dst_k,
-                       fuse ? 0 : (uint64_t)dst_v, key_dst, val_dst,
-                       fuse ? (int)fuse_rec_bytes : (aos ? 16 : 8));
+                       fused ? (uint64_t)fuse->out : (uint64_t)dst_k,
+                       fused ? 0 : (uint64_t)dst_v, key_dst, val_dst,
+                       fused ? (int)fuse->rec_bytes : (aos ? 16 : 8));
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemsetAsync(ticket, 0, 16, s));
     HIP_CHECK(hipMemsetAsync(desc, 0, (size_t)nb * PD * 8, s));
-    if (fuse) {
-      if (tie_flag) {
+    if (fused) {
+      if (tie) {
         // truncated sort: the passes so far ordered the pairs by the run
         // bits only; put the tied runs in order before the final digit
         hipLaunchKernelGGL(tie_repair_kernel,
                            dim3(os_num_tiles_t(n, TIE_TILE)), dim3(TIE_BS),
                            0, s, reinterpret_cast<uint64_t*>(src_k), n,
-                           tie_run_mask, tie_lo_mask, tie_flag);
+                           tie->run_mask, tie->lo_mask, tie->flag);
         HIP_CHECK(hipGetLastError());
       }
       hipLaunchKernelGGL(
@@ -1717,18 +1741,18 @@ static int onesweep_sort(uintptr_t keys, uintptr_t vals,
           dim3(nb), dim3(OS_AOS_BS), lds, s,
           reinterpret_cast<const uint64_t*>(src_k), nullptr, n, sb, desc,
           ticket, key_dst, val_dst, nullptr, sort_word,
-          reinterpret_cast<const uint32_t*>(fuse_recs),
-          fuse_rec_bytes / 4,
-          reinterpret_cast<const RecSegment*>(fuse_segs), fuse_nsegs);
+          reinterpret_cast<const uint32_t*>(fuse->recs),
+          fuse->rec_bytes / 4,
+          reinterpret_cast<const RecSegment*>(fuse->segs), fuse->nsegs);
       HIP_CHECK(hipGetLastError());
-      return cur;  // records land in fuse_out; pair buffers are dead
+      return cur;  // records land in fuse->out; pair buffers are dead
     } else if (aos) {
       hipLaunchKernelGGL(
           (onesweep_pass_kernel<true, OS_AOS_ITEMS, true, OS_AOS_BS>),
           dim3(nb), dim3(OS_AOS_BS), lds, s,
           reinterpret_cast<const uint64_t*>(src_k), nullptr, n, sb, desc,
           ticket, key_dst, val_dst, g_timing_buf, sort_word);
-    } else if (vals) {
+    } else if (b.vals) {
       hipLaunchKernelGGL(
           (onesweep_pass_kernel<true, OS_ITEMS, false, BLOCK>),
           dim3(nb), dim3(BLOCK), lds, s,
@@ -1757,41 +1781,18 @@ int onesweep_sort_pairs_u64(uintptr_t keys, uintptr_t vals,
                             uintptr_t tmp_keys, uintptr_t tmp_vals,
                             uint32_t n, int start_bit, int end_bit,
                             uintptr_t ws, uintptr_t stream) {
-  return onesweep_sort(keys, vals, tmp_keys, tmp_vals, n, start_bit, end_bit,
-                       ws, reinterpret_cast<hipStream_t>(stream), 0);
+  return onesweep_sort({keys, tmp_keys, vals, tmp_vals, PairLayout::SoA}, n,
+                       start_bit, end_bit, ws,
+                       reinterpret_cast<hipStream_t>(stream));
 }
 
+// sort_word = 1: the pairs order by their SECOND u64's bits (the aux word
+// of the wide-record path).
 int onesweep_sort_aos_u64(uintptr_t pairs, uintptr_t tmp_pairs, uint32_t n,
                           int start_bit, int end_bit, uintptr_t ws,
-                          uintptr_t stream) {
-  return onesweep_sort(pairs, 0, tmp_pairs, 0, n, start_bit, end_bit, ws,
-                       reinterpret_cast<hipStream_t>(stream), 1);
-}
-
-// sort_word = 1: pairs order by their SECOND u64's bits (the aux word of
-// the wide-record path — 80-bit keys sort as 16 aux bits then 64 prefix
-// bits across two calls, LSD-stable).
-int onesweep_sort_aos_word_u64(uintptr_t pairs, uintptr_t tmp_pairs,
-                               uint32_t n, int start_bit, int end_bit,
-                               uintptr_t ws, uintptr_t stream,
-                               int sort_word) {
-  return onesweep_sort(pairs, 0, tmp_pairs, 0, n, start_bit, end_bit, ws,
-                       reinterpret_cast<hipStream_t>(stream), 1, sort_word);
-}
-
-// sort + FUSED final gather: records land sorted in `out` (the last
-// pass's writeout copies whole records; the separate gather kernel and
-// the final pair round trip disappear). segs / nsegs: where the records
-// are when they are not contiguous from `recs` (record_src).
-int onesweep_sort_aos_fused_u64(uintptr_t pairs, uintptr_t tmp_pairs,
-                                uint32_t n, int start_bit, int end_bit,
-                                uintptr_t ws, uintptr_t stream,
-                                int sort_word, uintptr_t recs,
-                                uintptr_t out, uint32_t rec_bytes,
-                                uintptr_t segs, uint32_t nsegs) {
-  return onesweep_sort(pairs, 0, tmp_pairs, 0, n, start_bit, end_bit, ws,
-                       reinterpret_cast<hipStream_t>(stream), 1, sort_word,
-                       recs, out, rec_bytes, 0, 0, nullptr, segs, nsegs);
+                          uintptr_t stream, int sort_word) {
+  return onesweep_sort({pairs, tmp_pairs}, n, start_bit, end_bit, ws,
+                       reinterpret_cast<hipStream_t>(stream), sort_word);
 }
 
 // ---------------------------------------------------------------------------
@@ -1808,8 +1809,8 @@ int onesweep_sort_aos_fused_u64(uintptr_t pairs, uintptr_t tmp_pairs,
 // repair, using 8 * (m - 1) run bits more than the 8n rule (A/B knob)
 static int g_tie_repair = 1;
 void set_tie_repair(int m) { g_tie_repair = m < 0 ? 0 : m; }
-// path of the latest sort_records_truncated_u64 call: 0 = full sequence
-// only (by the caller), 1 = truncated, 2 = truncated then full fallback
+// path of the latest sort_records_u64 call: 0 = full sequence only,
+// 1 = truncated, 2 = truncated then full fallback
 static int g_last_sort_path = 0;
 int last_sort_path() { return g_last_sort_path; }
 int tie_repair_tile() { return TIE_TILE; }
@@ -1830,53 +1831,82 @@ void sort_records_plan(uint32_t n, int end_bit, int* lo_bit, int* passes,
   *passes = *lo_bit >= 8 ? rb / 8 + 1 : 0;
 }
 
-// Sorts the extracted pairs and writes the sorted RECORDS to `out`.
-// Returns the path taken (1 or 2), or -1 having done nothing when the
-// truncated sort is bypassed — `fuse` off, tie repair off, or no plan —
-// and the caller runs the full sequence itself. ws must be sized for the
-// full sequence (ceil(end_bit / 8) + 2 aux passes): the overflow flag
-// lives in the totals rows the shorter plan leaves unused.
-// BLOCKS on the stream once (the flag decides whether to fall back).
-int sort_records_truncated_u64(uintptr_t pairs, uintptr_t tmp_pairs,
-                               uint32_t n, int end_bit, int key_bytes,
-                               uintptr_t ws, uintptr_t stream,
-                               uintptr_t recs, uintptr_t out,
-                               uint32_t rec_bytes, int fuse, uintptr_t segs,
-                               uint32_t nsegs) {
+// Passes of the full sequence: the prefix digits of [0, end_bit) and, for
+// keys longer than the prefix, the two of the aux word.
+static int record_sort_passes(int end_bit, int key_bytes) {
+  end_bit = end_bit < 0 ? 0 : end_bit > 64 ? 64 : end_bit;
+  return (end_bit + 7) / 8 + (key_bytes > 8 ? 2 : 0);
+}
+
+// ws of sort_records_u64: the onesweep layout of the full sequence. The
+// tie-repair overflow flag has its word in every onesweep layout (the
+// ticket slot), so the truncated plan's own layout holds it.
+size_t sort_records_workspace_bytes(uint32_t n, int end_bit, int key_bytes) {
+  return onesweep_workspace_bytes(n, record_sort_passes(end_bit, key_bytes));
+}
+
+// The full LSD sequence over the 80-bit key, on the pairs as they stand in
+// b.keys: 16 aux bits first when the key has them, then the prefix bits
+// [0, end_bit). With `fuse` the final prefix pass writes the records to
+// t.out itself; without it, or with no pass to carry it (end_bit == 0),
+// the pairs are sorted plainly and gather_records moves the records.
+static void sort_records_full(PairBufs b, uint32_t n, int end_bit,
+                              int key_bytes, uintptr_t ws, hipStream_t s,
+                              const RecordTarget& t, bool fuse) {
+  if (key_bytes > 8 && onesweep_sort(b, n, 48, 64, ws, s, kAuxWord))
+    std::swap(b.keys, b.tmp_keys);
+  if (fuse && onesweep_sort(b, n, 0, end_bit, ws, s, kPrefixWord, &t) >= 0)
+    return;
+  if (onesweep_sort(b, n, 0, end_bit, ws, s)) std::swap(b.keys, b.tmp_keys);
+  gather_records(t.recs, b.keys, n, t.rec_bytes, /*dst_mode=*/0, t.out,
+                 /*dst_addr=*/0, /*dstart=*/0, /*shift=*/0, /*mask=*/0,
+                 /*func=*/0, /*nparts=*/0, reinterpret_cast<uintptr_t>(s),
+                 t.segs, t.nsegs);
+}
+
+// Sorts the extracted pairs and writes the sorted RECORDS to `out`, by the
+// truncated sort when `fuse` and tie repair are on and sort_records_plan
+// has a plan, else by the full sequence. Returns the path taken, which
+// last_sort_path() repeats. ws: sort_records_workspace_bytes.
+// BLOCKS on the stream once, and only after a truncated attempt (the flag
+// decides whether to fall back).
+int sort_records_u64(uintptr_t pairs, uintptr_t tmp_pairs, uint32_t n,
+                     int end_bit, int key_bytes, uintptr_t ws,
+                     uintptr_t stream, uintptr_t recs, uintptr_t out,
+                     uint32_t rec_bytes, int fuse, uintptr_t segs,
+                     uint32_t nsegs) {
   g_last_sort_path = 0;
-  if (end_bit > 64) end_bit = 64;
-  if (!fuse || !g_tie_repair || n == 0) return -1;
-  int lo_bit, passes, run_bits;
-  sort_records_plan(n, end_bit, &lo_bit, &passes, &run_bits);
-  if (passes == 0) return -1;
+  if (n == 0) return 0;
+  end_bit = end_bit < 0 ? 0 : end_bit > 64 ? 64 : end_bit;
   auto s = reinterpret_cast<hipStream_t>(stream);
+  PairBufs b{pairs, tmp_pairs};
+  const RecordTarget target{recs, out, segs, rec_bytes, nsegs};
+  int lo_bit, passes = 0, run_bits;
+  if (fuse && g_tie_repair)
+    sort_records_plan(n, end_bit, &lo_bit, &passes, &run_bits);
+  if (passes == 0) {
+    sort_records_full(b, n, end_bit, key_bytes, ws, s, target, fuse);
+    return 0;
+  }
+  // ws is sized for the full sequence; a plan leaves the low bits out
+  // (lo_bit >= 8: passes < ceil(end_bit / 8)), so its layout is shorter
   const int top = end_bit - 8;
   const uint64_t lo_mask = (1ull << lo_bit) - 1;
-  const uint64_t run_mask = ((1ull << top) - 1) & ~lo_mask;
-  // first bytes past what a `passes`-pass sort lays out in ws
-  uint32_t* flag = reinterpret_cast<uint32_t*>(
-      ws + onesweep_workspace_bytes(n, passes));
-  HIP_CHECK(hipMemsetAsync(flag, 0, 4, s));
-  int cur = onesweep_sort(pairs, 0, tmp_pairs, 0, n, lo_bit, end_bit, ws, s,
-                          1, 0, recs, out, rec_bytes, run_mask, lo_mask,
-                          flag, segs, nsegs);
-  // both fused calls here cover >= 2 digits (passes != 0), so they ran
+  TieRepair tie{((1ull << top) - 1) & ~lo_mask, lo_mask};
+  int cur = onesweep_sort(b, n, lo_bit, end_bit, ws, s, kPrefixWord, &target,
+                          &tie);
+  // the plan covers >= 2 digits, so the fused pass ran
   if (cur < 0) throw std::runtime_error("truncated sort: no pass ran");
   uint32_t overflow = 0;
-  HIP_CHECK(hipMemcpyAsync(&overflow, flag, 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(&overflow, tie.flag, 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   if (!overflow) return g_last_sort_path = 1;
   // some run was too long to repair: the full sequence on the pairs as
   // they now stand. Every step so far was stable, so equal full keys are
-  // still in input order and the LSD sort gives today's output; `out` is
+  // still in input order and the LSD sort gives the same output; `out` is
   // simply overwritten.
-  if (cur == 1) std::swap(pairs, tmp_pairs);
-  if (key_bytes > 8 &&
-      onesweep_sort(pairs, 0, tmp_pairs, 0, n, 48, 64, ws, s, 1, 1))
-    std::swap(pairs, tmp_pairs);
-  if (onesweep_sort(pairs, 0, tmp_pairs, 0, n, 0, end_bit, ws, s, 1, 0, recs,
-                    out, rec_bytes, 0, 0, nullptr, segs, nsegs) < 0)
-    throw std::runtime_error("sort fallback: no pass ran");
+  if (cur == 1) std::swap(b.keys, b.tmp_keys);
+  sort_records_full(b, n, end_bit, key_bytes, ws, s, target, fuse);
   return g_last_sort_path = 2;
 }
 

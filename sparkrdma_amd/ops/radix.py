@@ -31,6 +31,13 @@ def onesweep_passes(start_bit: int, end_bit: int) -> int:
     return -(-bits // 8) if bits > 0 else 0
 
 
+def sort_records_workspace_bytes(n: int, end_bit: int = 64,
+                                 key_bytes: int = 10) -> int:
+    """Bytes of ``ws`` that sort_records needs for n records: the native
+    figure (kernels.hip), which covers every path the sort can take."""
+    return load().sort_records_workspace_bytes(n, min(end_bit, 64), key_bytes)
+
+
 def _digit_windows(start_bit: int, end_bit: int):
     """The native sort calls, as (start_bit, end_bit) windows run in order,
     that leave the rows ordered by bits [start_bit, end_bit).
@@ -375,7 +382,7 @@ def sort_records(recs, rec_bytes: int, key_bytes: int = 8,
     With ``fuse`` and tie repair on (the default) the call BLOCKS on
     the current stream once: the truncated sort reads back a flag that
     says whether the full pass sequence must run after all. ``ws``, when
-    given, must be sized for the full sequence (as computed below).
+    given, needs sort_records_workspace_bytes(n, end_bit, key_bytes) bytes.
     """
     m = load()
     nbytes = recs if isinstance(recs, int) else recs.numel()
@@ -414,54 +421,22 @@ def sort_records(recs, rec_bytes: int, key_bytes: int = 8,
     else:
         assert tmp.numel() >= 2 * n
         tmp = tmp[:2 * n]
-    passes = -(-end_bit // 8) + (2 if key_bytes > 8 else 0)
-    need_ws = m.onesweep_workspace_bytes(n, passes)
+    need_ws = sort_records_workspace_bytes(n, end_bit, key_bytes)
     if ws is None:
         ws = torch.empty(need_ws, dtype=torch.uint8, device=dev)
     else:
         assert ws.numel() >= need_ws
-    cur, other = prs, tmp
     if out is None:
         out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     else:
         assert out.numel() >= nbytes
         out = out[:nbytes]
-    # truncated sort (kernels.hip sort_records_truncated_u64): LSD over the
-    # leading key bits only, tied runs repaired in LDS, full sequence as
-    # the fallback for inputs with long runs. -1 = bypassed (fuse off, tie
-    # repair off, or no plan for this n/end_bit): nothing ran, take the
-    # full sequence below. Path: last_sort_path().
-    if m.sort_records_truncated_u64(
-            cur.data_ptr(), other.data_ptr(), n, min(end_bit, 64),
-            key_bytes, ws.data_ptr(), _stream(), recs_ptr,
-            out.data_ptr(), rec_bytes, int(fuse), seg_ptr, nsegs) != -1:
-        return out
-    if key_bytes > 8:
-        # LSD over the 80-bit key: 16 aux bits first, then the prefix
-        r = m.onesweep_sort_aos_word_u64(cur.data_ptr(), other.data_ptr(),
-                                         n, 48, 64, ws.data_ptr(),
-                                         _stream(), 1)
-        if r == 1:
-            cur, other = other, cur
-    if fuse:
-        # the FINAL prefix pass writes whole records (kernels.hip
-        # FUSE_GATHER): the last pair writeout + the separate gather's
-        # pair re-read disappear. -1 = no pass ran at all (end_bit == 0)
-        # -> fall through to the plain path, whose gather writes `out`
-        res = m.onesweep_sort_aos_fused_u64(
-            cur.data_ptr(), other.data_ptr(), n, 0, min(end_bit, 64),
-            ws.data_ptr(), _stream(), 0, recs_ptr,
-            out.data_ptr(), rec_bytes, seg_ptr, nsegs)
-        if res != -1:
-            return out
-    r = m.onesweep_sort_aos_word_u64(cur.data_ptr(), other.data_ptr(), n,
-                                     0, min(end_bit, 64), ws.data_ptr(),
-                                     _stream(), 0)
-    if r == 1:
-        cur, other = other, cur
-    m.gather_records(recs_ptr, cur.data_ptr(), n, rec_bytes, 0,
-                     out.data_ptr(), 0, 0, 0, 0, 0, 0, _stream(),
-                     seg_ptr, nsegs)
+    # kernels.hip sort_records_u64: the truncated sort (LSD over the leading
+    # key bits only, tied runs repaired in LDS) where it applies, else or
+    # after it the full pass sequence. Path: last_sort_path().
+    m.sort_records_u64(prs.data_ptr(), tmp.data_ptr(), n, min(end_bit, 64),
+                       key_bytes, ws.data_ptr(), _stream(), recs_ptr,
+                       out.data_ptr(), rec_bytes, int(fuse), seg_ptr, nsegs)
     return out
 
 

@@ -450,11 +450,14 @@ class TeraSort:
         return self._rec_out_cache
 
     def _sort_ws(self):
-        from ..ops import load
+        from ..ops.radix import sort_records_workspace_bytes
         import torch
         cur = getattr(self, "_ws_cache", None)
-        need = load().onesweep_workspace_bytes(
-            int(self.n * 1.25) + 4096, 10)
+        # sized for sort_records on the full 80-bit key. sort_pairs_aos
+        # takes the same buffer: it needs at most 8 passes' worth, and the
+        # size only grows with the number of passes
+        need = sort_records_workspace_bytes(int(self.n * 1.25) + 4096,
+                                            end_bit=64, key_bytes=10)
         if cur is None or cur.numel() < need:
             self._ws_cache = torch.empty(need, dtype=torch.uint8,
                                          device="cuda")

@@ -354,9 +354,10 @@ def test_sort_word_one(hs):
         pairs = dev(pairs_np)
         tmp = Guarded(2 * n, torch.int64, 0x5A5A5A5A5A5A5A5A)
         ws = Guarded(hs.onesweep_workspace_bytes(n, 2), torch.uint8, 0xA5)
-        res = hs.onesweep_sort_aos_word_u64(
+        res = hs.onesweep_sort_aos_u64(
             pairs.data_ptr(), tmp.inner.data_ptr(), n, 48, 64,
-            ws.inner.data_ptr(), torch.cuda.current_stream().cuda_stream, 1)
+            ws.inner.data_ptr(), torch.cuda.current_stream().cuda_stream,
+            sort_word=1)
         assert res == 0, "two passes end in the input buffer"
         out = host(pairs).view(np.uint64)
         tmp.check(f"tmp n={n}")

@@ -1,12 +1,13 @@
-"""Truncated wide-record sort with tie repair (kernels.hip
-sort_records_truncated_u64) vs the numpy oracle, byte for byte: a stable
-argsort of the 80-bit key. Keys are built from the values
-sort_records_plan returns, so the position and length of every run in the
-run-bit order is known, and every test asserts the path the call took — a
-test of the new path must not pass by way of the fallback.
+"""Wide-record sort (kernels.hip sort_records_u64): the truncated sort with
+tie repair and the full pass sequence, vs the numpy oracle, byte for byte: a
+stable argsort of the 80-bit key. Keys of the truncated-sort tests are built
+from the values sort_records_plan returns, so the position and length of
+every run in the run-bit order is known, and every test asserts the path the
+call took — a test of one path must not pass by way of another.
 
 Every call sorts into a canary-guarded ``out`` with canary-guarded pair
-buffers and workspace; all guards must come back untouched."""
+buffers and a workspace of exactly sort_records_workspace_bytes bytes; all
+guards must come back untouched."""
 
 import numpy as np
 import pytest
@@ -46,21 +47,31 @@ def _check_guards(buf, what):
     assert np.all(got[-PAD:] == CANARY), what + ": written past the end"
 
 
-def _sort(hs, arr, key_bytes, end_bit=64):
+def _sort(hs, arr, key_bytes, end_bit=64, fuse=True, seg_lens=None):
     """sort_records with every buffer between canaries; returns (sorted
-    records, path taken)."""
+    records, path taken). ``seg_lens``: hand the records over as segments
+    of these lengths, each a buffer of its own, instead of contiguously."""
     import torch
-    from sparkrdma_amd.ops.radix import sort_records
+    from sparkrdma_amd.ops.radix import (sort_records,
+                                         sort_records_workspace_bytes)
     n, W = arr.shape
-    recs = torch.from_numpy(arr.reshape(-1)).cuda()
+    recs, segments = torch.from_numpy(arr.reshape(-1)).cuda(), None
+    if seg_lens is not None:
+        assert sum(seg_lens) == n
+        firsts = np.cumsum([0] + list(seg_lens[:-1]))
+        bufs = [recs[f * W:(f + c) * W].clone()
+                for f, c in zip(firsts, seg_lens)]
+        segments = [(int(f), c, b.data_ptr())
+                    for f, c, b in zip(firsts, seg_lens, bufs)]
+        recs = n * W
     out_buf, out = _guarded(n * W)
     pairs_buf, pairs = _guarded(n * 16)
     tmp_buf, tmp = _guarded(n * 16)
-    passes = -(-end_bit // 8) + (2 if key_bytes > 8 else 0)
-    ws_buf, ws = _guarded(hs.onesweep_workspace_bytes(n, passes))
+    ws_buf, ws = _guarded(sort_records_workspace_bytes(n, end_bit, key_bytes))
     res = sort_records(recs, W, key_bytes=key_bytes, end_bit=end_bit,
                        out=out, pairs=pairs.view(torch.int64),
-                       tmp=tmp.view(torch.int64), ws=ws)
+                       tmp=tmp.view(torch.int64), ws=ws, fuse=fuse,
+                       segments=segments)
     torch.cuda.synchronize()
     path = hs.last_sort_path()
     assert res.data_ptr() == out.data_ptr()
@@ -242,3 +253,94 @@ def test_bypassed_without_fuse(hs):
     assert hs.last_sort_path() == 0
     assert np.array_equal(out.cpu().numpy().reshape(arr.shape),
                           _oracle(arr, 10))
+
+
+# 8. the full pass sequence ------------------------------------------------
+
+def _shared_top(rng, n, W, end_bit):
+    """Records whose prefix bits from end_bit up are equal (all ones) and
+    random below; every fourth record repeats the full key of the one
+    before it, so ties occur at every end_bit."""
+    low = rng.integers(0, 1 << end_bit, n, dtype=np.uint64)
+    lo16 = rng.integers(0, 1 << 16, n, dtype=np.uint64)
+    dup = np.arange(3, n, 4)
+    low[dup], lo16[dup] = low[dup - 1], lo16[dup - 1]
+    above = np.uint64((((1 << (64 - end_bit)) - 1) << end_bit) & (2**64 - 1))
+    return _records(rng, above | low, lo16, W)
+
+
+def _full_sizes(hs):
+    """One tile; one record past a 4096-pair onesweep tile; several
+    tie-repair tiles."""
+    return (1, 4097, 3 * hs.tie_repair_tile() + 5)
+
+
+@pytest.mark.parametrize("end_bit", [64, 59, 8])
+@pytest.mark.parametrize("fuse", [True, False])
+@pytest.mark.parametrize("key_bytes", [8, 10])
+def test_full_sequence(hs, key_bytes, fuse, end_bit):
+    rng = np.random.default_rng(end_bit + key_bytes)
+    hs.set_tie_repair(0)
+    try:
+        for n in _full_sizes(hs):
+            arr = _shared_top(rng, n, 100, end_bit)
+            got, path = _sort(hs, arr, key_bytes, end_bit=end_bit, fuse=fuse)
+            assert path == 0, n
+            assert np.array_equal(got, _oracle(arr, key_bytes)), n
+    finally:
+        hs.set_tie_repair(1)
+
+
+@pytest.mark.parametrize("key_bytes", [8, 10])
+def test_end_bit_zero(hs, key_bytes):
+    """No prefix pass for the fused gather to ride: the plain gather must
+    write every record. Order: the low 16-bit word alone (key_bytes 10),
+    the input order (key_bytes 8)."""
+    rng = np.random.default_rng(key_bytes)
+    for n in _full_sizes(hs):
+        arr = _shared_top(rng, n, 100, 0)
+        got, path = _sort(hs, arr, key_bytes, end_bit=0, fuse=True)
+        assert path == 0, n
+        # `out` starts as canary bytes throughout: all of it is compared
+        if key_bytes == 8:
+            want = arr
+        else:
+            lo = arr[:, 8:10].copy().view("<u2").ravel()
+            want = arr[np.argsort(lo, kind="stable")]
+        assert np.array_equal(want, _oracle(arr, key_bytes)), n
+        assert np.array_equal(got, want), n
+
+
+@pytest.mark.parametrize("end_bit", [64, 59, 8])
+@pytest.mark.parametrize("key_bytes", [8, 10])
+def test_full_sequence_segmented(hs, key_bytes, end_bit):
+    """Three segments of unequal length, one a single record, through the
+    plain sort and gather_records: the contiguous result."""
+    n = 3 * hs.tie_repair_tile() + 5
+    arr = _shared_top(np.random.default_rng(end_bit), n, 100, end_bit)
+    hs.set_tie_repair(0)
+    try:
+        want, path_c = _sort(hs, arr, key_bytes, end_bit=end_bit, fuse=False)
+        got, path_s = _sort(hs, arr, key_bytes, end_bit=end_bit, fuse=False,
+                            seg_lens=[4097, 1, n - 4098])
+    finally:
+        hs.set_tie_repair(1)
+    assert (path_c, path_s) == (0, 0)
+    assert np.array_equal(want, _oracle(arr, key_bytes))
+    assert np.array_equal(got, want)
+
+
+def test_workspace_size(hs):
+    """sort_records_workspace_bytes covers the onesweep layout of the full
+    sequence, is at most one 16-byte slot larger, and grows with end_bit."""
+    from sparkrdma_amd.ops.radix import sort_records_workspace_bytes
+    for n in (1, 4096, 4097):
+        for key_bytes in (8, 10):
+            prev = 0
+            for end_bit in range(65):
+                passes = -(-end_bit // 8) + (2 if key_bytes > 8 else 0)
+                base = hs.onesweep_workspace_bytes(n, passes)
+                got = sort_records_workspace_bytes(n, end_bit, key_bytes)
+                assert base <= got <= base + 16, (n, key_bytes, end_bit)
+                assert got >= prev, (n, key_bytes, end_bit)
+                prev = got
