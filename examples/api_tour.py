@@ -156,7 +156,36 @@ def main():
         print(f"variable-length: {len(gk)} rows, {len(buf)} payload bytes, "
               f"{len(np.unique(gk))} groups")
 
-        # 7) metrics: the task/executor counters the reference feeds Spark
+        # 7) GROUP BY over wide rows: several aggregates per key ----------
+        # 24-byte rows: u64 key | i64 qty | f32 price | i32 flag. A column
+        # is (offset_bytes, dtype, op); integers reduce as int64, floats
+        # as float64. This is the numpy lane; on the GPU lane the rows
+        # are written with write_device_records(recs, 24, key_bytes=8),
+        # the results are device tensors and the rows are reduced where
+        # they lie (ops/csrc/reduce_records.hip).
+        n = 20_000
+        rows = np.zeros((n, 24), dtype=np.uint8)
+        rows[:, 0:8] = rng.integers(0, 50, n, dtype=np.uint64) \
+            .view(np.uint8).reshape(n, 8)
+        rows[:, 8:16] = rng.integers(1, 10, n).astype("<i8") \
+            .view(np.uint8).reshape(n, 8)
+        rows[:, 16:20] = rng.integers(1, 100, n).astype("<f4") \
+            .view(np.uint8).reshape(n, 4)
+        handle = eng.register_shuffle(num_maps=1, num_partitions=4)
+        writer = mgr.get_writer(handle, map_id=0)
+        writer.write_batch(rows[:, :8].copy().view(np.uint64).ravel(),
+                           rows[:, 8:])
+        writer.stop(True, partitioner=HashPartitioner(4))
+        gk, (qty, price_min, cnt) = mgr.get_reader(handle, 0, 3) \
+            .read_records_agg(24, [(8, "i64", "sum"), (16, "f32", "min"),
+                                   (None, None, "count")])
+        assert len(gk) == 50 and int(cnt.sum()) == n
+        assert int(qty.sum()) == int(rows[:, 8:16].copy().view("<i8").sum())
+        eng.unregister_shuffle(handle)
+        print(f"group by: {n} rows -> {len(gk)} keys, sum(qty) = "
+              f"{int(qty.sum())}, min(price) over all = {price_min.min():.0f}")
+
+        # 8) metrics: the task/executor counters the reference feeds Spark
         print("lifetime:", mgr.lifetime_metrics.format())
 
 

@@ -23,9 +23,9 @@ def ext_path() -> str:
 
 def sources():
     return [os.path.join(CSRC, f) for f in ("pool.cpp", "kernels.hip",
-                                            "reduce.hip", "bounds.hip",
-                                            "join.hip", "varlen.hip",
-                                            "bindings.cpp")]
+                                            "reduce.hip", "reduce_records.hip",
+                                            "bounds.hip", "join.hip",
+                                            "varlen.hip", "bindings.cpp")]
 
 
 def needs_build() -> bool:

@@ -144,6 +144,18 @@ PYBIND11_MODULE(_hipshuffle, m) {
   m.def("reduce_by_key_emit", &hs::reduce_by_key_emit, py::arg("pairs"),
         py::arg("n"), py::arg("op"), py::arg("ws"), py::arg("out_keys"),
         py::arg("out_vals"), py::arg("stream") = 0);
+  m.def("reduce_records_tile", &hs::reduce_records_tile);
+  m.def("reduce_records_max_columns", &hs::reduce_records_max_columns);
+  m.def("reduce_records_workspace_bytes",
+        &hs::reduce_records_workspace_bytes, py::arg("n"), py::arg("ncols"));
+  m.def("reduce_records_count", &hs::reduce_records_count, py::arg("pairs"),
+        py::arg("n"), py::arg("recs"), py::arg("rec_bytes"), py::arg("segs"),
+        py::arg("nsegs"), py::arg("col_words"), py::arg("col_types"),
+        py::arg("col_ops"), py::arg("ws"), py::arg("stream") = 0);
+  m.def("reduce_records_emit", &hs::reduce_records_emit, py::arg("pairs"),
+        py::arg("n"), py::arg("col_types"), py::arg("col_ops"),
+        py::arg("ws"), py::arg("g"), py::arg("out_keys"),
+        py::arg("out_vals"), py::arg("stream") = 0);
   m.def("join_expand_tile", &hs::join_expand_tile);
   m.def("join_expand_lds_rows", &hs::join_expand_lds_rows);
   m.def("join_probe_lds_keys", &hs::join_probe_lds_keys);

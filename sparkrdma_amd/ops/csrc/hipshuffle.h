@@ -139,6 +139,31 @@ void reduce_by_key_emit(uintptr_t pairs, uint32_t n, int op, uintptr_t ws,
                         uintptr_t out_keys, uintptr_t out_vals,
                         uintptr_t stream);
 
+// reduce_records.hip — segmented reduce of 1..8 typed columns of W-byte
+// records over key-sorted (key, aux) pairs; record index = aux & (2^48 - 1),
+// the records contiguous at `recs` or behind the segs / nsegs table of
+// gather_records. Column c is (col_words[c] = offset / 4, col_types[c]:
+// 0 i32, 1 u32, 2 i64, 3 f32, 4 f64, col_ops[c]: 0 sum, 1 min, 2 max,
+// 3 count — offset and type ignored). Integers reduce as i64, floats as f64.
+// Workspace: [scratch u64 x C*n][lead u64 x C*nb][base u64 x nb]
+// [heads u32 x nb] for nb = ceil(n / tile); the caller writes base[] =
+// exclusive scan of heads[] between the count and the emit call, g = their
+// total. Output: out_keys u64[g], column c at out_vals + c * g.
+int reduce_records_tile();
+int reduce_records_max_columns();
+size_t reduce_records_workspace_bytes(uint32_t n, int ncols);
+void reduce_records_count(uintptr_t pairs, uint32_t n, uintptr_t recs,
+                          uint32_t rec_bytes, uintptr_t segs, uint32_t nsegs,
+                          const std::vector<uint32_t>& col_words,
+                          const std::vector<int>& col_types,
+                          const std::vector<int>& col_ops, uintptr_t ws,
+                          uintptr_t stream);
+void reduce_records_emit(uintptr_t pairs, uint32_t n,
+                         const std::vector<int>& col_types,
+                         const std::vector<int>& col_ops, uintptr_t ws,
+                         uint64_t g, uintptr_t out_keys, uintptr_t out_vals,
+                         uintptr_t stream);
+
 // bounds.hip — pair extraction with the partition id in pair.x, found by
 // searching `nbounds` ascending u64 split points (device memory):
 // x = #{bounds <= key prefix}, unsigned; aux as extract_pairs writes it.

@@ -408,54 +408,10 @@ __global__ __launch_bounds__(BLOCK) void radix_scatter_kernel(
 // (source, destination) address pair per record in LDS; the block then
 // moves the records one word per lane.
 
-constexpr uint64_t AUX_IDX_MASK = (1ull << 48) - 1;  // aux = keylo16<<48 | idx
-
 struct GatherSlot {
   const uint32_t* src;  // first word of the record
   uint32_t* dst;        // first word of its destination slot
 };
-
-// Where record idx of a pair's aux word lives. Record indices are positions
-// in the reader's (virtual) arena; the records themselves may sit in
-// several places — a reader that takes its local blocks in place leaves
-// them in the shuffle's HBM blocks and copies only the rest into the arena
-// (reader.py record_segments). The caller passes a device table of nsegs
-// entries sorted by first_rec that cover [0, n) without gap or overlap;
-// record idx is record (idx - first_rec) of the LAST entry with
-// first_rec <= idx, counted from that entry's base. nsegs == 0: the
-// records are contiguous from `recs`, the plain address arithmetic, behind
-// a branch that is uniform for the whole grid (nsegs is a kernel argument).
-//
-// The table is searched in global memory: the flagship job has 86 entries,
-// one per fetch (16 bytes each, read by every block, so it stays in L2 and
-// the vector L1; 7 search steps cost its final pass 0.8 %,
-// profiles/r08_inplace_local_records.md), and the search runs once per
-// slot in the staging
-// loops, ahead of the record loads it addresses — copy_record_words never
-// sees it. An LDS copy would cap the table (the fused pass has under 4 KB
-// to spare before it loses its second resident block).
-struct RecSegment {
-  uint64_t first_rec;    // index of the segment's first record
-  const uint32_t* base;  // first word of that record
-};
-
-__device__ __forceinline__ const uint32_t* record_src(
-    const uint32_t* __restrict__ recs, const RecSegment* __restrict__ segs,
-    uint32_t nsegs, uint64_t idx, uint32_t w4) {
-  if (nsegs == 0) return recs + idx * w4;
-  // segs[lo].first_rec <= idx < segs[hi].first_rec (segs[0].first_rec is
-  // 0, hi == nsegs stands for +inf): only entries in [1, nsegs) are read
-  uint32_t lo = 0, hi = nsegs;
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (segs[mid].first_rec <= idx)
-      lo = mid;
-    else
-      hi = mid;
-  }
-  const RecSegment s = segs[lo];
-  return s.base + (idx - s.first_rec) * w4;
-}
 
 // independent record loads a lane issues before its first store
 constexpr int GATHER_BATCH = 8;  // 16: no faster, 90 / 160 VGPRs

@@ -440,6 +440,174 @@ def sort_records(recs, rec_bytes: int, key_bytes: int = 8,
     return out
 
 
+def _record_source(recs, rec_bytes: int, segments, device=None):
+    """(byte count, n, device, recs pointer, segment table or None, nsegs,
+    checked segment triples or None) of a record buffer given the
+    sort_records way: a tensor, or an extent plus ``segments``."""
+    nbytes = recs if isinstance(recs, int) else recs.numel()
+    n = nbytes // rec_bytes
+    if segments is None:
+        if isinstance(recs, int):
+            raise ValueError("recs may be a byte count only with segments")
+        return nbytes, n, recs.device, recs.data_ptr(), None, 0, None
+    dev = (recs.device if isinstance(recs, torch.Tensor)
+           else device if device is not None
+           else torch.device("cuda", torch.cuda.current_device()))
+    if n == 0:
+        return nbytes, 0, dev, 0, None, 0, []
+    ptr, table, nsegs, segs = _segment_table(segments, n, rec_bytes, dev)
+    return nbytes, n, dev, ptr, table, nsegs, segs
+
+
+def _empty_columns(cols, dev):
+    from ..aggregate import column_is_float
+    return (torch.empty(0, dtype=torch.int64, device=dev),
+            [torch.empty(0, dtype=torch.float64 if column_is_float(t, o)
+                         else torch.int64, device=dev)
+             for _off, t, o in cols])
+
+
+def reduce_records_workspace_bytes(n: int, ncols: int) -> int:
+    """Bytes of ``ws`` that reduce_records_by_key needs for n pairs and
+    ncols columns: the widened-value scratch and the per-tile tables."""
+    return load().reduce_records_workspace_bytes(n, ncols)
+
+
+def reduce_records_by_key(pairs: torch.Tensor, recs, rec_bytes: int, columns,
+                          segments=None,
+                          out_keys: Optional[torch.Tensor] = None,
+                          out_vals: Optional[torch.Tensor] = None,
+                          ws: Optional[torch.Tensor] = None):
+    """Reduce up to 8 typed columns of W-byte records per key, without
+    moving a record (reduce_records.hip). ``pairs`` is an int64 tensor of
+    2n elements, interleaved (key, aux) as extract_pairs writes them with
+    equal keys adjacent (all 64 bits; 8-byte keys only); record
+    ``aux & (2^48 - 1)`` of ``recs`` belongs to a pair. ``recs`` /
+    ``segments`` are sort_records': a uint8 tensor, or an extent (tensor or
+    byte count) plus ``(first_rec, nrec, device_ptr)`` runs. Pairs and
+    records are left unchanged.
+
+    ``columns`` is a sequence of ``(offset_bytes, dtype, op)``, dtype in
+    ("i32", "u32", "i64", "f32", "f64"), op in ("sum", "min", "max",
+    "count"); for "count" dtype and offset may be None. The dtype decides
+    the accumulator: integers reduce as int64 (i32 sign-, u32 zero-extended;
+    sums wrap), floats as float64 in a fixed order, so a float sum is
+    bit-reproducible for a given pair order wherever the records lie.
+
+    Returns ``(keys int64[g], [one tensor[g] per column])``, one row per
+    run in input order; a column is float64 for f32 / f64 dtypes, int64
+    otherwise. The columns are views of one [C, g] buffer.
+
+    BLOCKS on the current stream once, to read back the number of runs g.
+    ``out_keys`` (int64, >= g), ``out_vals`` (int64, >= C * g) and ``ws``
+    (uint8, >= reduce_records_workspace_bytes(n, C)) may be supplied by the
+    caller; one that is too small raises ValueError before anything is
+    written to it. With ``segments`` the memory behind the pointers must
+    stay valid until the call has run on the stream."""
+    from ..aggregate import check_columns, column_is_float
+    cols = check_columns(columns, rec_bytes)
+    C = len(cols)
+    n = pairs.numel() // 2
+    if n >= 1 << 32:
+        raise ValueError("reduce_records_by_key handles n < 2^32 records")
+    _nbytes, nrec, dev, recs_ptr, seg_t, nsegs, _segs = _record_source(
+        recs, rec_bytes, segments, pairs.device)
+    if n == 0:
+        return _empty_columns(cols, pairs.device)
+    if nrec == 0:
+        raise ValueError("pairs without records")
+    m = load()
+    nb = -(-n // m.reduce_records_tile())
+    need_ws = m.reduce_records_workspace_bytes(n, C)
+    if ws is None:
+        ws = torch.empty(need_ws, dtype=torch.uint8, device=pairs.device)
+    elif ws.numel() < need_ws:
+        raise ValueError(f"ws too small: {ws.numel()} < {need_ws} bytes")
+    s = _stream()
+    words = [off // 4 for off, _t, _o in cols]
+    types = [t for _off, t, _o in cols]
+    ops = [o for _off, _t, o in cols]
+    m.reduce_records_count(pairs.data_ptr(), n, recs_ptr, rec_bytes,
+                           seg_t.data_ptr() if seg_t is not None else 0,
+                           nsegs, words, types, ops, ws.data_ptr(), s)
+    # workspace layout (hipshuffle.h): [scratch u64 x C*n][lead u64 x C*nb]
+    # [base u64 x nb][heads u32 x nb]; the scan over nb tile counts is
+    # plumbing
+    base_off = 8 * C * (n + nb)
+    heads = ws[base_off + 8 * nb:base_off + 12 * nb].view(torch.int32)
+    incl = torch.cumsum(heads, 0, dtype=torch.int64)
+    ws[base_off:base_off + 8 * nb].view(torch.int64).copy_(incl - heads)
+    g = int(incl[-1])                       # syncs the stream
+    for name, t, need in (("out_keys", out_keys, g),
+                          ("out_vals", out_vals, C * g)):
+        if t is not None and t.numel() < need:
+            raise ValueError(f"{name} holds {t.numel()} elements, the "
+                             f"input has {g} runs: {need} needed")
+    if out_keys is None:
+        out_keys = torch.empty(g, dtype=torch.int64, device=pairs.device)
+    if out_vals is None:
+        out_vals = torch.empty(C * g, dtype=torch.int64, device=pairs.device)
+    m.reduce_records_emit(pairs.data_ptr(), n, types, ops, ws.data_ptr(), g,
+                          out_keys.data_ptr(), out_vals.data_ptr(), s)
+    vals = []
+    for c, (_off, t, o) in enumerate(cols):
+        v = out_vals[c * g:(c + 1) * g]
+        vals.append(v.view(torch.float64) if column_is_float(t, o) else v)
+    return out_keys[:g], vals
+
+
+def aggregate_records(recs, rec_bytes: int, columns, end_bit: int = 64,
+                      segments=None, pairs: Optional[torch.Tensor] = None,
+                      tmp: Optional[torch.Tensor] = None,
+                      ws: Optional[torch.Tensor] = None):
+    """GROUP BY over W-byte AoS records with a u64 LE key at offset 0:
+    extract (key, index) pairs, sort them by key bits [0, end_bit)
+    (callers whose keys share their top bits pass a smaller end_bit and
+    save radix passes), reduce ``columns`` per key with
+    reduce_records_by_key. No record is moved or copied; ``recs`` /
+    ``segments`` are sort_records'. Returns ``(keys int64[g], [one
+    tensor[g] per column])`` with the keys ascending (unsigned).
+
+    ``pairs`` and ``tmp`` (int64, >= 2n) are the pair buffers of the sort;
+    ``ws`` (uint8) serves the sort and then the reduction and needs the
+    larger of onesweep_workspace_bytes(n, onesweep_passes(0, end_bit)) and
+    reduce_records_workspace_bytes(n, C). BLOCKS once, in the reduction."""
+    from ..aggregate import check_columns
+    cols = check_columns(columns, rec_bytes)
+    if not 1 <= end_bit <= 64:
+        raise ValueError("end_bit must be in [1, 64]")
+    if rec_bytes < 8:
+        raise ValueError("records hold a u64 key: rec_bytes >= 8")
+    _nbytes, n, dev, _ptr, _seg_t, _nsegs, segs = _record_source(
+        recs, rec_bytes, segments)
+    if n == 0:
+        return _empty_columns(cols, dev)
+    if n >= 1 << 32:
+        raise ValueError("aggregate_records handles n < 2^32 records")
+    m = load()
+    need_ws = max(m.onesweep_workspace_bytes(n, onesweep_passes(0, end_bit)),
+                  m.reduce_records_workspace_bytes(n, len(cols)))
+    if ws is None:
+        ws = torch.empty(need_ws, dtype=torch.uint8, device=dev)
+    elif ws.numel() < need_ws:
+        raise ValueError(f"ws too small: {ws.numel()} < {need_ws} bytes")
+    if segments is None:
+        prs = extract_pairs(recs, rec_bytes, 8, pairs)
+    else:
+        if pairs is None:
+            pairs = torch.empty(2 * n, dtype=torch.int64, device=dev)
+        if pairs.numel() < 2 * n:
+            raise ValueError("pairs too small")
+        prs = pairs[:2 * n]
+        for first, cnt, ptr in segs:
+            m.extract_pairs(ptr, cnt, rec_bytes, 8,
+                            prs.data_ptr() + 16 * first, _stream(),
+                            idx_base=first)
+    prs = sort_pairs_aos(prs, 0, end_bit, tmp=tmp, ws=ws)
+    return reduce_records_by_key(prs, recs, rec_bytes, columns,
+                                 segments=segments, ws=ws)
+
+
 def gather_grouped(recs: torch.Tensor, pairs_grouped: torch.Tensor, n: int,
                    rec_bytes: int, counts: np.ndarray, dst_addr: np.ndarray,
                    shift: int, mask: int, func: int = 0,

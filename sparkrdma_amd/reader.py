@@ -904,6 +904,89 @@ class ShuffleReader:
             while bio.tell() < end:
                 yield pickle.load(bio)
 
+    # ---------------- wide records reduced per key ----------------------
+
+    def read_records_agg(self, record_bytes: int, columns,
+                         end_bit: int = 64):
+        """GROUP BY over the whole partition range of ``record_bytes``-byte
+        AoS records with a u64 LE key at offset 0 — what
+        ``write_device_records(recs, W, key_bytes=8)`` and
+        ``write_batch(keys, values[n, W - 8])`` both write. ``columns`` is
+        a sequence of ``(offset_bytes, dtype, op)``, dtype in ("i32",
+        "u32", "i64", "f32", "f64"), op in ("sum", "min", "max", "count")
+        (aggregate.check_columns). Returns ``(keys, [one array per
+        column])``: one row per distinct key, keys ascending by bits
+        [0, end_bit) (callers whose partitions share top key bits pass a
+        smaller end_bit); keys are int64 holding the u64 bits, a column is
+        float64 for f32 / f64 dtypes and int64 otherwise (sums wrap).
+
+        With the GPU data plane these are device tensors and no record is
+        moved: ops.radix.aggregate_records sorts (key, index) pairs and
+        ops/csrc/reduce_records.hip reads each record's column bytes where
+        the record lies — for a reader opened with ``records=(W, 8,
+        pairs)`` through ``record_segments()``, so a block left in place
+        (``in_place=True``) is neither copied nor moved. The pairs are
+        re-extracted per segment, whatever the fused fetch already wrote.
+        LIFETIME, as for sort_records over ``record_segments()``: the
+        caller synchronises the GPU before ``unregister_shuffle``.
+        Without the GPU plane the result is numpy
+        (aggregate.reduce_records_np)."""
+        from .aggregate import check_columns, reduce_records_np
+        check_columns(columns, record_bytes)
+        if record_bytes < 8:
+            raise ValueError("records hold a u64 key: record_bytes >= 8")
+        if not 1 <= end_bit <= 64:
+            raise ValueError("end_bit must be in [1, 64]")
+        spec = self.fetcher._records
+        if spec is not None:
+            if spec[1] != 8:
+                raise ValueError(f"read_records_agg handles 8-byte keys; "
+                                 f"the reader's record spec has "
+                                 f"key_bytes={spec[1]}")
+            if spec[0] != record_bytes:
+                raise ValueError(f"record_bytes={record_bytes} disagrees "
+                                 f"with the reader's record spec "
+                                 f"({spec[0]} bytes)")
+        elif self._fixed_records:
+            raise ValueError("in_place=True needs a records= spec")
+        mgr = self.manager
+        if mgr.gpu is not None:
+            import torch
+            from .ops.radix import aggregate_records
+            for _ in self.fetcher:
+                pass
+            if spec is not None:
+                total = self.fetcher.total_bytes
+                if total % record_bytes:
+                    raise ValueError(f"{total} fetched bytes are not whole "
+                                     f"{record_bytes}-byte records")
+                with torch.cuda.device(mgr.gpu.device):
+                    return aggregate_records(
+                        total, record_bytes, columns, end_bit=end_bit,
+                        segments=self.fetcher.record_segments())
+            arena = self.fetcher.arena
+            if arena is None:
+                arena = torch.empty(0, dtype=torch.uint8,
+                                    device=f"cuda:{mgr.gpu.device}")
+            arena = arena.view(torch.uint8)
+            if arena.numel() % record_bytes:
+                raise ValueError(f"{arena.numel()} fetched bytes are not "
+                                 f"whole {record_bytes}-byte records")
+            return aggregate_records(arena, record_bytes, columns,
+                                     end_bit=end_bit)
+        # ---- CPU path: numpy mirror of the device semantics ----
+        import numpy as np
+        blocks = []
+        for _ref, data in self.fetcher:
+            blk = np.frombuffer(bytes(data), dtype=np.uint8)
+            if len(blk) % record_bytes:
+                raise ValueError(f"a fetched block of {len(blk)} bytes is "
+                                 f"not whole {record_bytes}-byte records")
+            blocks.append(blk)
+        recs = (np.concatenate(blocks) if blocks
+                else np.empty(0, np.uint8)).reshape(-1, record_bytes)
+        return reduce_records_np(recs, columns, end_bit)
+
     # ---------------- variable-length rows (varlen.py) -----------------
 
     def read_varlen(self, ordering: bool = False, end_bit: int = 64):
