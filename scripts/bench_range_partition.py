@@ -10,9 +10,10 @@ into R partitions (default 512), uniform u64 keys in every arm:
 wide   100-byte records. RangePartitioner.uniform(R) (func 0, top bits)
        against bounds sampled from the keys (func 4). The two lanes
        differ in the extract kernel only (extract_pairs against
-       extract_pairs_bounds) and in the digit of hist / scatter / gather
-       (top key bits against the stored pid). R > 4096 adds the
-       two-level pid radix to both lanes alike.
+       extract_pairs_bounds) and, at 257 <= R <= 4096, in the digit of
+       hist / scatter / gather (top key bits against the stored pid).
+       R <= 256 takes the fused route in both lanes (ids counted, one
+       fused pass); R > 4096 adds the two-level pid radix to both alike.
 pairs  16-byte (key, value) records. uniform(R) takes the direct
        scatter; bounds take the record lane (pairs + gather).
 

@@ -4,6 +4,9 @@ Run on a GPU box:  python scripts/bench_record_movement.py [--gb 4]
 Times, for 100-byte and 256-byte records:
   * gather_records dst_mode 0 (records -> sorted output, random permutation)
   * gather_records dst_mode 1 (records -> 256 per-digit destinations)
+  * the map-side record move into 256 partitions: gather_records mode 1
+    over grouped pairs against partition_records_fused over pairs in input
+    order (--only-partition runs these alone)
   * sort_records(fuse=True)   (pair extract + radix passes + fused gather)
   * sort_records with the tie repair on and off, on random keys and on
     all-equal keys (the input that forces the fallback to the full passes)
@@ -125,6 +128,59 @@ def bench_width(hs, W, total_bytes, launches):
     sort_case("sort equal keys", 0)
 
 
+def bench_partition(hs, W, total_bytes, launches):
+    """The record move of the map-side write into 256 partitions (top 8 key
+    bits): gather_records mode 1 over pairs already grouped by partition
+    (the last of the three kernels of that route; random record reads)
+    against partition_records_fused over the pairs in input order (the
+    whole route after the counts; a tile's reads are one contiguous span).
+    Both write the same bytes to the same places. A build without the fused
+    entry times the gather only."""
+    n = (total_bytes // W) & ~1
+    dev = "cuda"
+    s = torch.cuda.current_stream().cuda_stream
+    g = torch.Generator(device=dev)
+    g.manual_seed(W + 2)
+    recs = torch.randint(-2**63, 2**63 - 1, (n * W // 8,), dtype=torch.int64,
+                         device=dev, generator=g).view(torch.uint8)
+    out = torch.empty(n * W, dtype=torch.uint8, device=dev)
+    keyw = recs.view(n, W)[:, :8].contiguous().view(torch.int64).view(n)
+    digit = (keyw >> 56) & 255
+    idx = torch.arange(n, dtype=torch.int64, device=dev)
+    counts = torch.bincount(digit, minlength=256)
+    starts = torch.cumsum(counts, 0) - counts
+    dst_addr = out.data_ptr() + starts * W
+
+    order = torch.argsort(digit, stable=True)
+    grouped = torch.stack([keyw[order], idx[order] | (0x5A5A << 48)], 1) \
+        .contiguous()
+    del order
+    dstart = starts.to(torch.int32)
+    ms = timed_ms(lambda: hs.gather_records(
+        recs.data_ptr(), grouped.data_ptr(), n, W, 1, 0,
+        dst_addr.data_ptr(), dstart.data_ptr(), 56, 255, 0, 0, s), launches)
+    report("partition: gather mode 1", W, n, ms)
+    del grouped
+    if not hasattr(hs, "partition_records_fused"):
+        return
+    want = out[:min(n * W, 1 << 28)].clone()
+    out.zero_()
+    pairs = torch.stack([digit, idx | (0x5A5A << 48)], 1).contiguous()
+    del digit, idx, keyw
+    ws = torch.empty(hs.partition_records_workspace_bytes(n),
+                     dtype=torch.uint8, device=dev)
+    totals = torch.empty(256, dtype=torch.int32, device=dev)
+    ms = timed_ms(lambda: hs.count_pair_digits(
+        pairs.data_ptr(), n, totals.data_ptr(), s), launches)
+    report("partition: count_pair_digits", W, n, ms)
+    assert torch.equal(totals.to(torch.int64), counts)
+    ms = timed_ms(lambda: hs.partition_records_fused(
+        pairs.data_ptr(), n, recs.data_ptr(), W, dst_addr.data_ptr(),
+        ws.data_ptr(), s), launches)
+    report("partition: fused pass", W, n, ms)
+    assert torch.equal(out[:want.numel()], want), "fused pass != gather"
+
+
 def bench_fetch(hs, W, total_bytes, launches):
     """Fetch n W-byte records into an arena and produce their pairs: plain
     copy + extract_pairs against the fused kernel. src sits 4 and dst 12
@@ -171,15 +227,23 @@ def main():
     ap.add_argument("--launches", type=int, default=11)
     ap.add_argument("--only-fetch", action="store_true",
                     help="run only the reduce-side fetch cases")
+    ap.add_argument("--only-partition", action="store_true",
+                    help="run only the map-side partition cases at 100 "
+                         "bytes (the run to collect counters over)")
     args = ap.parse_args()
     if args.launches < 10:
         ap.error("--launches must be at least 10")
     if not torch.cuda.is_available():
         sys.exit("bench_record_movement needs a GPU")
     hs = load()
+    if args.only_partition:
+        bench_partition(hs, 100, int(args.gb * 1e9), args.launches)
+        return
     for W in (100, 256):
         if not args.only_fetch:
             bench_width(hs, W, int(args.gb * 1e9), args.launches)
+            torch.cuda.empty_cache()
+            bench_partition(hs, W, int(args.gb * 1e9), args.launches)
             torch.cuda.empty_cache()
         bench_fetch(hs, W, int(args.gb * 1e9), args.launches)
         torch.cuda.empty_cache()

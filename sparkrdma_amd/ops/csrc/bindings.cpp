@@ -127,6 +127,14 @@ PYBIND11_MODULE(_hipshuffle, m) {
         py::arg("stream"), py::arg("recs"), py::arg("out"),
         py::arg("rec_bytes"), py::arg("fuse") = 1, py::arg("segs") = 0,
         py::arg("nsegs") = 0, py::call_guard<py::gil_scoped_release>());
+  m.def("count_pair_digits", &hs::count_pair_digits, py::arg("pairs"),
+        py::arg("n"), py::arg("totals"), py::arg("stream") = 0);
+  m.def("partition_records_workspace_bytes",
+        &hs::partition_records_workspace_bytes, py::arg("n"));
+  m.def("partition_records_fused", &hs::partition_records_fused,
+        py::arg("pairs"), py::arg("n"), py::arg("recs"),
+        py::arg("rec_bytes"), py::arg("dst_table"), py::arg("ws"),
+        py::arg("stream") = 0);
   m.def("onesweep_sort_aos_u64", &hs::onesweep_sort_aos_u64,
         py::arg("pairs"), py::arg("tmp_pairs"), py::arg("n"),
         py::arg("start_bit"), py::arg("end_bit"), py::arg("ws"),

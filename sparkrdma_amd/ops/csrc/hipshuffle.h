@@ -115,6 +115,18 @@ int sort_records_u64(uintptr_t pairs, uintptr_t tmp_pairs, uint32_t n,
                      uint32_t nsegs = 0);
 // bytes of its ws, whichever path it takes
 size_t sort_records_workspace_bytes(uint32_t n, int end_bit, int key_bytes);
+// Map-side partition of wide records by a digit of at most 8 bits, which
+// pair.x holds (the partition id). count_pair_digits: totals u32[256] = how
+// many of the n pairs have each id. partition_records_fused: record
+// pair.y & (2^48 - 1) of `recs` goes to dst_table[pair.x] (device u64[256],
+// 4-byte-aligned byte addresses; entries of empty partitions are never
+// dereferenced) behind the same partition's earlier records, in one pass.
+void count_pair_digits(uintptr_t pairs, uint32_t n, uintptr_t totals,
+                       uintptr_t stream);
+size_t partition_records_workspace_bytes(uint32_t n);
+void partition_records_fused(uintptr_t pairs, uint32_t n, uintptr_t recs,
+                             uint32_t rec_bytes, uintptr_t dst_table,
+                             uintptr_t ws, uintptr_t stream);
 void set_tie_repair(int m);
 int last_sort_path();
 int tie_repair_tile();

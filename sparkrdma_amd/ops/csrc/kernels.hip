@@ -19,7 +19,9 @@
 //     digit's run is a contiguous global write burst).
 //   * partition path: 3-kernel (hist -> hierarchical scan -> scatter;
 //     row-major [nb][ND] hist so every access is thread==digit coalesced)
-//     because the host must see counts to lay out HBM blocks first.
+//     because the host must see counts to lay out HBM blocks first
+//     (wide records into at most 256 partitions: counts, then ONE fused
+//     onesweep pass — see 'wide-record machinery').
 //   * sort path: onesweep — one kernel per pass with decoupled lookback
 //     (u64 flag|count agent-scope descriptors), AoS records, deferred
 //     walk; selectable hist+scan mode kept for A/B.
@@ -846,15 +848,26 @@ __global__ void onesweep_digit_bases_kernel(
 // TeraSort is 10 B key + 90 B value = 100 B records).
 //
 // Design: records stay put while 16-byte (sortkey, aux) PAIRS flow
-// through the existing radix machinery, then ONE gather pass moves each
-// W-byte record to its final position:
-//   * extract_pairs: record -> (key-prefix u64, aux = keylo16<<48 | idx)
-//   * partition/sort the pairs (existing kernels; `key_word` selects
-//     which u64 of the pair the digit comes from, so the 80-bit key
-//     sorts as 16 aux bits then 64 prefix bits, LSD-stable)
-//   * gather_records: walk the grouped/sorted pairs linearly, copy record
-//     idx to its slot — writes are linear (W-byte runs), reads are
-//     W-byte contiguous chunks; both sides move each record exactly once.
+// through the existing radix machinery, and each W-byte record moves
+// once, to its final position:
+//   * extract_pairs: record -> (key-prefix u64, aux = keylo16<<48 | idx);
+//     on the map side pair.x is the record's PARTITION ID instead
+//   * sort (reduce side): LSD passes over the pairs (`sort_word` selects
+//     which u64 of the pair the digit comes from, so the 80-bit key sorts
+//     as 16 aux bits then 64 prefix bits, LSD-stable); the FINAL pass
+//     writes the records instead of the pairs (FUSE_GATHER)
+//   * partition (map side), up to 256 partitions: count the ids
+//     (count_pair_digits) so the host can lay out the HBM blocks, then
+//     that same fused pass, once, with the block addresses as its
+//     per-digit bases (partition_records_fused). No grouped copy of the
+//     pairs and no separate gather; the pairs enter in input order, so a
+//     tile's record reads cover one contiguous span of the source
+//   * partition, 257..4096 partitions: hist -> scan -> radix_scatter
+//     groups the pairs, gather_records (dst_mode 1) then walks the grouped
+//     pairs linearly and copies record idx to its slot — writes are linear
+//     (W-byte runs), reads are W-byte contiguous chunks. More than 4096:
+//     the same after a two-level grouping of the pairs by partition id
+// Both sides move each record exactly once.
 // Traffic: ~2.2x the record bytes + ~64 B/pass for the 16 B pairs —
 // pair passes cost 16% of what full-record passes would at W = 100.
 // extract_pairs itself re-reads practically every 128-byte line of its
@@ -1586,6 +1599,50 @@ size_t onesweep_workspace_bytes(uint32_t n, int passes) {
          (size_t)nb * 256 * 8;
 }
 
+// The parts of a ws of onesweep_workspace_bytes(n, passes) bytes.
+struct OnesweepWs {
+  uint32_t* totals;   // [passes][256]
+  uint64_t* key_dst;  // [256]
+  uint64_t* val_dst;  // [256]
+  uint32_t* ticket;   // 4 words: ticket, tie flag, pad
+  uint64_t* desc;     // [nb][256]
+};
+static inline OnesweepWs onesweep_ws(uintptr_t ws, int passes) {
+  OnesweepWs w;
+  w.totals = reinterpret_cast<uint32_t*>(ws);
+  w.key_dst = reinterpret_cast<uint64_t*>(w.totals + (size_t)passes * 256);
+  w.val_dst = w.key_dst + 256;
+  w.ticket = reinterpret_cast<uint32_t*>(w.val_dst + 256);
+  w.desc = reinterpret_cast<uint64_t*>(w.ticket + 4);
+  return w;
+}
+
+// Dynamic LDS of one pass kernel, and the attribute that lets a launch ask
+// for it (more than the 64 KB default), set once on every instantiation
+// that is launched: by onesweep_sort and by partition_records_fused.
+constexpr size_t OS_LDS_SOA = (size_t)OS_TILE * 8 + (size_t)NW * 256 * 4 +
+                              256 * 4 * 2 + BLOCK * 4 + 16 + OS_TILE;
+constexpr size_t OS_LDS_AOS = (size_t)OS_TILE * 16 +
+                              (size_t)(OS_AOS_BS / kWave) * 256 * 4 +
+                              256 * 4 * 2 + OS_AOS_BS * 4 + 16;
+static void onesweep_allow_lds() {
+  static bool attr_set = false;
+  if (attr_set) return;
+  for (const void* f :
+       {reinterpret_cast<const void*>(
+            &onesweep_pass_kernel<true, OS_ITEMS, false, BLOCK>),
+        reinterpret_cast<const void*>(
+            &onesweep_pass_kernel<false, OS_ITEMS, false, BLOCK>),
+        reinterpret_cast<const void*>(
+            &onesweep_pass_kernel<true, OS_AOS_ITEMS, true, OS_AOS_BS>),
+        reinterpret_cast<const void*>(
+            &onesweep_pass_kernel<true, OS_AOS_ITEMS, true, OS_AOS_BS,
+                                  true>)})
+    (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              160 * 1024 - 1024);
+  attr_set = true;
+}
+
 // The two buffers a sort ping-pongs between. AoS: keys / tmp_keys point at
 // interleaved (key, val) 16-byte pairs and vals / tmp_vals are unused.
 // SoA: keys and vals are separate u64 arrays (vals may be 0: keys only).
@@ -1630,11 +1687,10 @@ static int onesweep_sort(PairBufs b, uint32_t n, int start_bit, int end_bit,
     throw std::runtime_error("fused sort: nsegs without a table");
   uint32_t nb = os_num_tiles(n);
   int passes = (end_bit - start_bit + PBITS - 1) / PBITS;
-  uint32_t* totals = reinterpret_cast<uint32_t*>(ws);
-  uint64_t* key_dst = reinterpret_cast<uint64_t*>(totals + (size_t)passes * PD);
-  uint64_t* val_dst = key_dst + PD;
-  uint32_t* ticket = reinterpret_cast<uint32_t*>(val_dst + PD);
-  uint64_t* desc = reinterpret_cast<uint64_t*>(ticket + 4);
+  const OnesweepWs w = onesweep_ws(ws, passes);
+  uint32_t* totals = w.totals;
+  uint64_t *key_dst = w.key_dst, *val_dst = w.val_dst, *desc = w.desc;
+  uint32_t* ticket = w.ticket;
   if (tie) tie->flag = ticket + 1;
   HIP_CHECK(hipMemsetAsync(totals, 0, (size_t)passes * PD * 4, s));
   uint32_t hist_grid = nb < 1024 ? (nb ? nb : 1) : 1024;
@@ -1643,28 +1699,9 @@ static int onesweep_sort(PairBufs b, uint32_t n, int start_bit, int end_bit,
                      reinterpret_cast<const uint64_t*>(b.keys), n, start_bit,
                      passes, totals, aos ? 2 : 1, sort_word);
   HIP_CHECK(hipGetLastError());
-  size_t lds_soa = (size_t)OS_TILE * 8 + (size_t)NW * PD * 4 +
-                   PD * 4 * 2 + BLOCK * 4 + 16 + OS_TILE;
-  size_t lds_aos = (size_t)OS_TILE * 16 +
-                   (size_t)(OS_AOS_BS / kWave) * PD * 4 + PD * 4 * 2 +
-                   OS_AOS_BS * 4 + 16;
-  size_t lds = aos ? lds_aos : lds_soa;
-  static bool attr_set = false;
-  if (!attr_set) {
-    for (const void* f :
-         {reinterpret_cast<const void*>(
-              &onesweep_pass_kernel<true, OS_ITEMS, false, BLOCK>),
-          reinterpret_cast<const void*>(
-              &onesweep_pass_kernel<false, OS_ITEMS, false, BLOCK>),
-          reinterpret_cast<const void*>(
-              &onesweep_pass_kernel<true, OS_AOS_ITEMS, true, OS_AOS_BS>),
-          reinterpret_cast<const void*>(
-              &onesweep_pass_kernel<true, OS_AOS_ITEMS, true, OS_AOS_BS,
-                                    true>)})
-      (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024 - 1024);
-    attr_set = true;
-  }
+  static_assert(PD == 256, "OS_LDS_* are written for 8-bit digits");
+  const size_t lds = aos ? OS_LDS_AOS : OS_LDS_SOA;
+  onesweep_allow_lds();
   uintptr_t src_k = b.keys, src_v = b.vals, dst_k = b.tmp_keys,
             dst_v = b.tmp_vals;
   int cur = 0;
@@ -1749,6 +1786,76 @@ int onesweep_sort_aos_u64(uintptr_t pairs, uintptr_t tmp_pairs, uint32_t n,
                           uintptr_t stream, int sort_word) {
   return onesweep_sort({pairs, tmp_pairs}, n, start_bit, end_bit, ws,
                        reinterpret_cast<hipStream_t>(stream), sort_word);
+}
+
+// ---------------------------------------------------------------------------
+// Map-side partition of wide records in one fused pass (digits of at most
+// 8 bits). The pairs carry the record's partition id in pair.x, so the
+// digit is the id and the fused pass kernel of the sort is the whole job:
+// it ranks a tile of pairs, finds the tile's place in every partition by
+// look-back and writes the tile's records in per-partition runs, in input
+// order. The per-digit record bases are the caller's block addresses, in
+// place of the output of onesweep_digit_bases_kernel. The pairs enter in
+// input order, so the records a tile reads are one contiguous span of the
+// source.
+
+// The 256 totals of pair.x's low byte over n pairs, for the caller's
+// layout. No per-tile matrix, no scan.
+void count_pair_digits(uintptr_t pairs, uint32_t n, uintptr_t totals,
+                       uintptr_t stream) {
+  if (pairs % 16 || totals % 4)
+    throw std::runtime_error(
+        "count_pair_digits: pairs need 16-byte, totals 4-byte alignment");
+  auto s = reinterpret_cast<hipStream_t>(stream);
+  HIP_CHECK(hipMemsetAsync(reinterpret_cast<void*>(totals), 0, 256 * 4, s));
+  if (n == 0) return;
+  const uint32_t nb = os_num_tiles(n);
+  hipLaunchKernelGGL((onesweep_hist_all_kernel<10, 8>),
+                     dim3(nb < 1024 ? nb : 1024), dim3(BLOCK), 0, s,
+                     reinterpret_cast<const uint64_t*>(pairs), n,
+                     /*start_bit=*/0, /*passes=*/1,
+                     reinterpret_cast<uint32_t*>(totals), /*in_stride=*/2,
+                     /*word_off=*/0);
+  HIP_CHECK(hipGetLastError());
+}
+
+size_t partition_records_workspace_bytes(uint32_t n) {
+  return onesweep_workspace_bytes(n, 1);
+}
+
+// Record idx = pair.y & (2^48 - 1) of `recs` goes to dst_table[pair.x],
+// behind the records of the same partition that precede it in the pairs.
+// dst_table: device u64[256] of 4-byte-aligned byte addresses; the entry
+// of a partition no pair names is never read past the table. pair.x < 256
+// and idx < the record count of `recs` are the caller's to guarantee.
+// ws: partition_records_workspace_bytes(n), 8-byte aligned.
+void partition_records_fused(uintptr_t pairs, uint32_t n, uintptr_t recs,
+                             uint32_t rec_bytes, uintptr_t dst_table,
+                             uintptr_t ws, uintptr_t stream) {
+  if (rec_bytes % 4 || rec_bytes < 4)
+    throw std::runtime_error("rec_bytes must be a positive multiple of 4");
+  if (pairs % 16 || recs % 4 || dst_table % 8 || ws % 8)
+    throw std::runtime_error(
+        "partition_records_fused: pairs need 16-byte, recs 4-byte, "
+        "dst_table and ws 8-byte alignment");
+  if (n == 0) return;
+  if (!pairs || !recs || !dst_table || !ws)
+    throw std::runtime_error("partition_records_fused: null argument");
+  auto s = reinterpret_cast<hipStream_t>(stream);
+  const uint32_t nb = os_num_tiles(n);
+  const OnesweepWs w = onesweep_ws(ws, 1);
+  onesweep_allow_lds();
+  HIP_CHECK(hipMemsetAsync(w.ticket, 0, 16, s));
+  HIP_CHECK(hipMemsetAsync(w.desc, 0, (size_t)nb * 256 * 8, s));
+  hipLaunchKernelGGL(
+      (onesweep_pass_kernel<true, OS_AOS_ITEMS, true, OS_AOS_BS, true>),
+      dim3(nb), dim3(OS_AOS_BS), OS_LDS_AOS, s,
+      reinterpret_cast<const uint64_t*>(pairs), nullptr, n, /*shift=*/0,
+      w.desc, w.ticket, reinterpret_cast<const uint64_t*>(dst_table),
+      /*val_dst=*/nullptr, /*timing=*/nullptr, /*sort_word=*/kPrefixWord,
+      reinterpret_cast<const uint32_t*>(recs), rec_bytes / 4,
+      /*rec_segs=*/nullptr, /*rec_nsegs=*/0);
+  HIP_CHECK(hipGetLastError());
 }
 
 // ---------------------------------------------------------------------------

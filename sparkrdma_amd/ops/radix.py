@@ -7,7 +7,7 @@ in tests, not here).
 
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -628,20 +628,95 @@ def gather_grouped(recs: torch.Tensor, pairs_grouped: torch.Tensor, n: int,
                           _stream())
 
 
-def group_records(recs: torch.Tensor, rec_bytes: int, pairs: torch.Tensor,
-                  n: int, shift: int, nbits_eff: int, hist: torch.Tensor,
-                  counts: np.ndarray, dst_addr: np.ndarray, func: int = 0,
-                  nparts: int = 0) -> None:
-    """Single-pass tail of a record partition, after digit_counts and the
-    caller's layout: group the pairs by digit (scatter_pairs), then move
-    digit d's records, in input order, to dst_addr[d] onward
-    (gather_grouped). ``counts`` are all 2^nbits_eff digit totals."""
+FUSED_DIGIT_BITS = 8    # widest digit of the fused record partition
+
+
+class RecordDigits(NamedTuple):
+    """What count_record_digits hands to group_records."""
+    pairs: torch.Tensor
+    n: int
+    counts: np.ndarray              # int64[2^nbits_eff] digit totals
+    # digits wider than FUSED_DIGIT_BITS only: digit_counts' per-tile
+    # matrix and the (shift, nbits_eff, func, nparts) it was counted under
+    hist: Optional[torch.Tensor] = None
+    digit: tuple = ()
+
+
+def count_record_digits(recs: torch.Tensor, rec_bytes: int, key_bytes: int,
+                        shift: int, nbits_eff: int, func: int = 0,
+                        nparts: int = 0,
+                        bounds: Optional[torch.Tensor] = None
+                        ) -> RecordDigits:
+    """First half of a single-pass record partition: extract the pairs and
+    count the digit (shift, nbits_eff, func, nparts — or a search of
+    ``bounds``) of every record, so that the caller can lay out its
+    destinations. BLOCKS on the current stream to read the totals back.
+
+    Digits of at most FUSED_DIGIT_BITS bits: pair.x holds the digit itself,
+    whichever partition function produced it, and count_pair_digits totals
+    it in one read of the pairs. Wider digits keep the prefix (or the
+    searched id) in pair.x and digit_counts' per-tile matrix for the
+    scatter of group_records."""
+    n = recs.numel() // rec_bytes
+    if n >= 1 << 32:
+        raise ValueError("a record partition handles n < 2^32 records")
+    nd = 1 << nbits_eff
+    if nbits_eff <= FUSED_DIGIT_BITS:
+        pairs = extract_pairs(recs, rec_bytes, key_bytes, bounds=bounds,
+                              pid=(func, shift, nd - 1, nparts))
+        totals = torch.empty(1 << FUSED_DIGIT_BITS, dtype=torch.int32,
+                             device=recs.device)
+        load().count_pair_digits(pairs.data_ptr(), n, totals.data_ptr(),
+                                 _stream())
+        counts = totals.cpu().numpy().astype(np.int64)  # syncs the stream
+        return RecordDigits(pairs, n, counts[:nd])
+    pairs = extract_pairs(recs, rec_bytes, key_bytes, bounds=bounds)
+    if bounds is not None:
+        # hist / scatter / gather read the searched id as plain bits
+        func, shift, nparts = 0, 0, 0
+    hist, totals = digit_counts(pairs.data_ptr(), n, shift, nbits_eff,
+                                recs.device, func, 2, nparts)
+    counts = totals.cpu().numpy().astype(np.int64)      # syncs the stream
+    return RecordDigits(pairs, n, counts, hist,
+                        (shift, nbits_eff, func, nparts))
+
+
+def group_records(recs: torch.Tensor, rec_bytes: int, digits: RecordDigits,
+                  dst_addr: np.ndarray) -> None:
+    """Second half, after the caller's layout: move digit d's records, in
+    input order, to the device byte address dst_addr[d] onward (int64
+    numpy, one entry per digit; entries of empty digits are not used).
+
+    Digits of at most FUSED_DIGIT_BITS bits take ONE pass, the fused pass
+    kernel of the sort with the digit bases replaced by ``dst_addr``
+    (kernels.hip partition_records_fused): no grouped copy of the pairs,
+    no separate gather. Wider digits group the pairs (scatter_pairs) and
+    then gather the records (gather_grouped).
+
+    The workspace and the address table are dropped on return while the
+    pass may still be queued; see digit_counts for why that is safe."""
+    pairs, n = digits.pairs, digits.n
+    if digits.hist is None:
+        if (np.asarray(dst_addr) % 4).any():
+            raise ValueError("destination addresses must be 4-byte aligned")
+        m = load()
+        table = np.zeros(1 << FUSED_DIGIT_BITS, dtype=np.int64)
+        table[:len(dst_addr)] = dst_addr
+        table_t = torch.from_numpy(table).to(recs.device)
+        ws = torch.empty(m.partition_records_workspace_bytes(n),
+                         dtype=torch.uint8, device=recs.device)
+        m.partition_records_fused(pairs.data_ptr(), n, recs.data_ptr(),
+                                  rec_bytes, table_t.data_ptr(),
+                                  ws.data_ptr(), _stream())
+        return
+    shift, nbits_eff, func, nparts = digits.digit
     pairs_out = torch.empty_like(pairs)
-    starts_t = torch.from_numpy(np.cumsum(counts) - counts).to(recs.device)
-    scatter_pairs(pairs, n, shift, nbits_eff, hist,
+    starts_t = torch.from_numpy(np.cumsum(digits.counts) - digits.counts) \
+        .to(recs.device)
+    scatter_pairs(pairs, n, shift, nbits_eff, digits.hist,
                   pairs_out.data_ptr() + starts_t * 16, func, nparts)
-    gather_grouped(recs, pairs_out, n, rec_bytes, counts, dst_addr, shift,
-                   (1 << nbits_eff) - 1, func, nparts)
+    gather_grouped(recs, pairs_out, n, rec_bytes, digits.counts, dst_addr,
+                   shift, (1 << nbits_eff) - 1, func, nparts)
 
 
 def partition_records(recs: torch.Tensor, rec_bytes: int,
@@ -658,14 +733,12 @@ def partition_records(recs: torch.Tensor, rec_bytes: int,
         shift = 64 - nbits
     _check_small_digit(nbits, shift, func)
     nbits_eff = max(nbits, 4)
-    pairs = extract_pairs(recs, rec_bytes, key_bytes)
-    hist, totals = digit_counts(pairs.data_ptr(), n, shift, nbits_eff,
-                                recs.device, func, 2, nparts)
-    counts = totals.cpu().numpy().astype(np.int64)  # syncs the stream
+    digits = count_record_digits(recs, rec_bytes, key_bytes, shift,
+                                 nbits_eff, func, nparts)
+    counts = digits.counts
     out = torch.empty_like(recs)
     dst = out.data_ptr() + (np.cumsum(counts) - counts) * rec_bytes
-    group_records(recs, rec_bytes, pairs, n, shift, nbits_eff, hist, counts,
-                  dst, func, nparts)
+    group_records(recs, rec_bytes, digits, dst)
     return counts[:1 << nbits], out
 
 

@@ -609,14 +609,22 @@ class ShuffleWriter:
         return counts_full, pairs_f, mask_full
 
     def _commit_gpu_records(self, partitioner) -> None:
-        """Wide-record map-side GPU write. Records stay put while 16-byte
-        (key-prefix, aux) pairs run the radix machinery; ONE gather pass
-        then moves each W-byte record straight to its final HBM position
-        (ops/csrc/kernels.hip 'wide-record machinery'). Replaces the
+        """Wide-record map-side GPU write. Every record moves once, from
+        where the task left it straight to its final HBM position
+        (ops/csrc/kernels.hip 'wide-record machinery'); only 16-byte pairs
+        run the radix machinery before that. Up to 256 partitions (a digit
+        of at most 8 bits): the pairs carry the partition id, whether bits,
+        range, hash or split points produced it; their ids are counted for
+        the block layout, and ONE fused pass ranks the pairs, finds every
+        tile's place in its partitions and writes the records there, in
+        input order (ops/radix.py count_record_digits / group_records).
+        Digits of 9 to 12 bits group the pairs through the per-tile
+        histogram matrix and then gather the records; more than 4096
+        partitions group the pairs in two levels first. Replaces the
         reference's CPU writer + mmap + register for arbitrary-width
         records (RdmaMappedFile.java:113-189)."""
         import torch
-        from .ops.radix import (digit_counts, extract_pairs, gather_grouped,
+        from .ops.radix import (count_record_digits, gather_grouped,
                                 group_records)
         if self.manager.gpu is None:
             raise RuntimeError("GPU writer requires the GPU data plane")
@@ -646,16 +654,15 @@ class ShuffleWriter:
             layout = _GpuLayout(self, counts * W, R, dev)
             gather_grouped(recs, grouped, n, W, counts, layout.dst, 0, mask)
         else:
-            pairs = extract_pairs(recs, W, key_bytes, bounds=bounds)
-            if bounds is not None:
-                # hist / scatter / gather read the pid as plain bits
-                func, shift, nparts = 0, 0, 0
-            hist, totals = digit_counts(pairs.data_ptr(), n, shift,
-                                        nbits_eff, dev, func, 2, nparts)
-            counts = totals.cpu().numpy().astype(np.int64)  # syncs
+            digits = count_record_digits(recs, W, key_bytes, shift,
+                                         nbits_eff, func, nparts, bounds)
+            counts = digits.counts                          # synced
+            if counts[R:].any():
+                # such a record would have no destination block
+                raise ValueError("partitioner produced an id >= "
+                                 f"{R} on the GPU")
             layout = _GpuLayout(self, counts[:R] * W, 1 << nbits_eff, dev)
-            group_records(recs, W, pairs, n, shift, nbits_eff, hist, counts,
-                          layout.dst, func, nparts)
+            group_records(recs, W, digits, layout.dst)
         layout.finish(n)
 
     # -- variable-length rows -------------------------------------------
